@@ -48,6 +48,13 @@ Extra objects on the JSON line:
                  work is fixed ("strong"): the driver's N = 1, 2, 4, 8 runs give the scaling curve of the north
                  star's "column-sharded LDE"; `lde_ms` is the phase its >= 6x target refers to.
   --mode lde-commit runs only that last measurement and prints it as the line's `value` (GB/s algorithmic).
+
+--full   : a plain run (`bench.py --gpus N --steps K --warmup W`) sets up, settles, warms up, times the K steps and prints the line:
+           the headline and nothing else.  Every object above -- `roofline` (per-kernel events, measured traffic), the transform
+           variants, `cpu_baseline`, the secondary objects and `sharded_lde_commit` -- is measured only with --full.
+--dump-outputs DIR : after the timed steps, what the last one left in rank 0's columns (the transformed columns a caller receives)
+           goes to DIR/*.npy (_dump_outputs).  The settle phase runs for a time, not a number of steps, so the columns are put back
+           to their seeded inputs before the warm-up: with the same arguments the outputs are the same from run to run.
 """
 import argparse
 import json
@@ -199,7 +206,7 @@ def _measure_traffic(log_n):
         for counters in (("FETCH_SIZE",), ("WRITE_SIZE",), ("SQ_INSTS_VALU", "SQ_ACTIVE_INST_VALU", "SQ_BUSY_CYCLES")):
             out = os.path.join(work, counters[0])
             cmd = ["rocprofv3", "--kernel-trace", "--pmc", *counters, "-d", out, "-o", "t", "--output-format", "csv", "--", sys.executable,
-                   os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--cols", "2", "--log-n", str(log_n), "--no-cpu-baseline", "--no-extras", "--settle", "0.3"]
+                   os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--cols", "2", "--log-n", str(log_n), "--no-cpu-baseline", "--no-extras", "--settle", "0.3", "--full"]
             env = dict(os.environ, MS_BENCH_NO_PMC="1", TMPDIR="/tmp")
             pr = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
             try:
@@ -300,6 +307,24 @@ def _spawn_ranks(n):
     return 0
 
 
+DUMP_SEED = 0x64756D70
+DUMP_BYTES = 48_000_000       # float64 arrays of one dump, in all: well below 64 MB
+
+
+def _dump_outputs(path, cols):
+    """--dump-outputs: the columns as the last timed step left them, at a fixed seeded sample of positions (the same for every column
+    and every run; all of them when the columns are small).  The words are Goldilocks residues below 2^64, so each goes out as its low
+    and high 32 bits, both exact in float64: ntt_columns_lo.npy, ntt_columns_hi.npy (columns x positions) and ntt_positions.npy."""
+    n = len(cols[0])
+    m = min(n, 1 << 18, DUMP_BYTES // (8 * (2 * len(cols) + 1)))
+    pos = np.arange(n) if m == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=m, replace=False))
+    words = np.stack([c.to_numpy()[pos] for c in cols])
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "ntt_columns_lo.npy"), (words & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(path, "ntt_columns_hi.npy"), (words >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(path, "ntt_positions.npy"), pos.astype(np.float64))
+
+
 def _latest_traffic_json():
     import glob
     hits = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_ntt_traffic.json")))
@@ -317,12 +342,16 @@ def main():
     ap.add_argument("--settle", type=float, default=1.0, help="seconds of untimed transforms before the warm-up steps (clock ramp)")
     ap.add_argument("--traffic-json", default=_latest_traffic_json(), help="JSON file with PMC-derived HBM bytes per transform (default: the newest profiles/rNN_ntt_traffic.json)")
     ap.add_argument("--mode", choices=["ntt", "lde-commit"], default="ntt", help="lde-commit: only the column-sharded LDE + commitment (any N)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the lde_commit / prove / sharded objects")
+    ap.add_argument("--full", action="store_true", help="also measure everything besides the headline: roofline, variants, CPU baseline, "
+                                                        "the secondary and sharded objects (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy (float64)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the lde_commit / prove / sharded objects")
     ap.add_argument("--pmc-child", action="store_true", help="internal: every object's workload between marker launches, under rocprofv3 --pmc")
     ap.add_argument("--cold-child", action="store_true", help="internal: a fresh process's first proof (bench_cold_start)")
     ap.add_argument("--log-rows", type=int, default=22, help="--mode lde-commit: rows of the trace (configs[4]: 2^22)")
     ap.add_argument("--total-cols", type=int, default=32, help="--mode lde-commit: columns of the trace, sharded over the ranks")
     args = ap.parse_args()
+    extras = args.full and not args.no_extras
 
     if args.cold_child:
         _cold_child_main()
@@ -429,6 +458,7 @@ def main():
     P = (1 << 64) - (1 << 32) + 1
     host_cols = [rng.integers(0, P, size=n, dtype=np.uint64) for _ in range(args.cols)]
     cols = [GpuVec.from_numpy(pl, c) for c in host_cols]
+    inputs = [c.clone() for c in cols]
     dom = Radix2EvaluationDomain.new_coset(n, 7)
     fft = GpuFft(dom, GOLDILOCKS_FP, pl)
 
@@ -441,6 +471,9 @@ def main():
     while time.perf_counter() - t_settle < args.settle:
         fft.enqueue(cols)
         pl.sync()
+    # however many transforms the settle ran, the W + K steps start from the seeded inputs (device copies on the library's stream)
+    for c, x in zip(cols, inputs):
+        pl.lib.check(pl.lib.ms_copy(pl.handle, c.ptr, x.ptr, c.words * 8))
     for _ in range(args.warmup):
         fft.enqueue(cols)
     barrier()
@@ -450,13 +483,18 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed = reduce_max(elapsed)
+    for x in inputs:
+        x.free()
+    if args.dump_outputs and rank == 0:                         # before anything below transforms the columns again
+        _dump_outputs(args.dump_outputs, cols)
 
-    # per-kernel durations, measured live with hipEvents on the library's stream
-    pl.profile(True)
-    for _ in range(max(2, min(args.steps, 5))):
-        fft.enqueue(cols)
-    prof = pl.profile_read()
-    pl.profile(False)
+    prof = {}
+    if args.full:                                                # per-kernel durations, measured live with hipEvents on the library's stream
+        pl.profile(True)
+        for _ in range(max(2, min(args.steps, 5))):
+            fft.enqueue(cols)
+        prof = pl.profile_read()
+        pl.profile(False)
 
     # The column-sharded LDE + commitment runs on every rank (RCCL inside the library).  It is guarded: the headline
     # measurement above is complete at this point, so if the exchange raises -- or hangs: N > 1 has never run on
@@ -501,7 +539,7 @@ def main():
             timer.cancel()
 
     if rank != 0:
-        if not args.no_extras:
+        if extras:
             run_sharded_guarded()
         if dist is not None:
             dist.destroy_process_group()
@@ -535,15 +573,16 @@ def main():
                    "columns_per_gpu": args.cols, "log_n": log_n, "parallelism": f"columns x{world}"},
         "field_ops_per_s": round(field_ops * total_cols * args.steps / elapsed, 1),
         "us_per_transform": round(elapsed / args.steps / args.cols * 1e6, 2),
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source, "traffic_kernels": traffic_kernels,
-                     "kernel": "ntt2_first_pass + 2 x ntt2_mid_pass: the three radix-256 passes of one forward coset transform",
-                     "algorithmic_bytes_per_transform": alg_bytes_col,
-                     "us_per_transform_events": round(us_per_transform, 2), "kernels": kernels},
     }
+    if args.full:
+        out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source, "traffic_kernels": traffic_kernels,
+                           "kernel": "ntt2_first_pass + 2 x ntt2_mid_pass: the three radix-256 passes of one forward coset transform",
+                           "algorithmic_bytes_per_transform": alg_bytes_col,
+                           "us_per_transform_events": round(us_per_transform, 2), "kernels": kernels}
     out["multi_gpu_note"] = ("2 / 4 / 8 ranks unmeasured on hardware from this repository (one GPU per lease); rehearsed on the simulator + fake RCCL, tests/test_bench_multirank.py"
                              if world == 1 else f"{world} ranks, one process per GPU, RCCL")
-    if world == 1:
+    if args.full and world == 1:
         # for information: the other transforms of configs[1] on the same columns (wall time per transform, 5 steps each)
         from ministark_amd import GpuIfft
         variants = {}
@@ -575,12 +614,12 @@ def main():
             variants["single_column_repeated_us_per_transform"] = round((time.perf_counter() - t1) / 40 * 1e6, 2)
             plan.close()
         out["variants"] = variants
-    if not args.no_extras:
+    if extras:
         state["line"] = dict(out)                                # what rank 0 prints if the exchange never returns
         sharded = run_sharded_guarded()                          # every rank takes part
     if sharded is not None:
         out["sharded_lde_commit"] = sharded
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras:
         for c in cols:
             c.free()
         out["c2_sweep"] = bench_c2_sweep(pl)
@@ -590,7 +629,7 @@ def main():
         out["constraint_eval"] = bench_constraint_eval(pl, not args.no_cpu_baseline)
         out["prove"] = bench_prove(pl, not args.no_cpu_baseline)
         out["cold_start"] = bench_cold_start()
-    if not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed on rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:     # the CPU baseline is timed on rank 0 at N = 1 only
         from oracle import cref
         x = host_cols[0].copy()
         cref.ntt(x[: 1 << 16], 16, 1, False, 7)          # warm the OpenMP pool
@@ -605,7 +644,7 @@ def main():
         out["cpu_baseline"] = {"value": round(alg_bytes_col / best / 1e9, 3), "unit": "GB/s", "cores": cref.num_threads(),
                                "kind": "port", "ms_per_transform": round(best * 1e3, 2),
                                "sample": f"{reps} x one 2^{log_n} column, forward coset NTT, oracle/c (C/OpenMP restatement, not the reference binary)"}
-    if world == 1 and not args.no_extras:                        # counters last: nothing is timed after a profiler session
+    if world == 1 and extras:                                    # counters last: nothing is timed after a profiler session
         pl.sync()
         measured = _measure_traffic(log_n)
         if measured is not None:
@@ -615,10 +654,11 @@ def main():
                 out["roofline"]["valu_insts_per_element"] = round(wave_insts * 64.0 / n, 1)
                 out["roofline"]["frac_of_valu_issue_peak"] = round(wave_insts / (us_per_transform * 1e-6) / VALU_ISSUE_PEAK, 4)
         _attach_all({k: out[k] for k in ("lde_commit", "lde_2_24", "constraint_eval", "prove") if isinstance(out.get(k), dict)}, _measure_objects())
-    if traffic is None and args.traffic_json and os.path.exists(args.traffic_json):
-        traffic = json.load(open(args.traffic_json)).get("hbm_bytes_per_transform")
-        traffic_source = os.path.relpath(args.traffic_json, ROOT)
-    out["roofline"].update({"traffic": traffic, "traffic_source": traffic_source, "traffic_kernels": traffic_kernels})
+    if args.full:
+        if traffic is None and args.traffic_json and os.path.exists(args.traffic_json):
+            traffic = json.load(open(args.traffic_json)).get("hbm_bytes_per_transform")
+            traffic_source = os.path.relpath(args.traffic_json, ROOT)
+        out["roofline"].update({"traffic": traffic, "traffic_source": traffic_source, "traffic_kernels": traffic_kernels})
     _emit(out)
     if dist is not None:
         dist.destroy_process_group()

@@ -1,10 +1,10 @@
 #!/bin/bash
 # Run on the GPU box (gpurun): the measurements DESIGN.md sections 4 and 6 and bench.py's `roofline.traffic` cite.
 #   scripts/collect_profiles.sh rNN
-#   1. bench.py (default command) under rocprofv3 --kernel-trace --stats      -> per-kernel average durations
+#   1. bench.py --full under rocprofv3 --kernel-trace --stats                 -> per-kernel average durations
 #   2. the same workload under --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, no tracing domains)
 #   3. SQ counters of the NTT passes and of the SHA-256 commit phase
-#   4. plain bench.py JSON line, scripts/bench_configs.py, scripts/bench_commit.py, the C2 sweep
+#   4. the bench.py --full JSON line, scripts/bench_configs.py, scripts/bench_commit.py, the C2 sweep
 # Raw outputs land in gpurun_out/profiles_raw/ and are REDUCED HERE, on the box that produced them, into
 # gpurun_out/profiles_raw/summary/rNN_* (scripts/summarise_profiles.py); those files are what goes to profiles/.
 # Round 3 lost its SQ counter file to the size filter below and a summary was then made from the previous round's copy that
@@ -19,10 +19,10 @@ rm -rf $OUT; mkdir -p $OUT
 date +%s.%N > $OUT/RUN_STAMP
 cd $R
 FAIL=0
-python bench.py > $OUT/bench.json 2> $OUT/bench.err         # the one line (< 4 KiB) ...
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err    # the one line (< 4 KiB) ...
 cp $R/bench_detail.json $OUT/bench_detail.json                # ... and the full record it summarises (round 6)
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o ntt --output-format csv -- python bench.py --no-cpu-baseline --no-extras > $OUT/stats.log 2>&1
-PM="python bench.py --steps 2 --warmup 1 --cols 2 --no-cpu-baseline --no-extras --settle 0.3"
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o ntt --output-format csv -- python bench.py --full --no-cpu-baseline --no-extras > $OUT/stats.log 2>&1
+PM="python bench.py --full --steps 2 --warmup 1 --cols 2 --no-cpu-baseline --no-extras --settle 0.3"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o ntt --output-format csv -- $PM > $OUT/pmc_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o ntt --output-format csv -- $PM > $OUT/pmc_write.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY GRBM_GUI_ACTIVE -d $OUT/pmc_sq -o ntt --output-format csv -- $PM > $OUT/pmc_sq.log 2>&1

@@ -11,7 +11,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOY = ["--log-n", "12", "--cols", "2", "--steps", "2", "--warmup", "1", "--settle", "0", "--log-rows", "8", "--total-cols", "8", "--no-cpu-baseline"]
+TOY = ["--log-n", "12", "--cols", "2", "--steps", "2", "--warmup", "1", "--settle", "0", "--log-rows", "8", "--total-cols", "8", "--no-cpu-baseline",
+       "--full"]                                           # the sharded objects of the default mode are measured with --full only
 
 
 def _env(**extra):
@@ -56,7 +57,8 @@ def test_lde_commit_mode_n_ranks(world):
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_default_mode_n_ranks(world):
-    """the driver's own command shape (`bench.py --gpus N --steps K --warmup W`), toy sizes: weak-scaling headline + the sharded objects"""
+    """the driver's own command shape (`bench.py --gpus N --steps K --warmup W`) with --full, toy sizes: weak-scaling headline + the
+    sharded objects"""
     one = _baseline(["--mode", "lde-commit"])              # (the default mode with ONE rank also runs every single-GPU object: not on the simulator)
     r, lines = _run(TOY + ["--gpus", str(world)], _env())
     assert r.returncode == 0, r.stderr.decode()[-2000:]

@@ -171,25 +171,42 @@ def test_evaluator_arm_uses_the_opcodes_of_the_header_and_the_signature_of_eval_
     params = [p.strip() for p in sig.strip().rstrip(",").split(",\n")]
     assert params == ["expr: &Expr<AlgebraicItem<FieldVariant<Fp, Fq>>>", "challenges: &[Fq]", "hints: &[Fq]", "lde_step: usize",
                       "domain_offset: Fp", "x_lde: &[Fp]", "base_trace_lde_cols: &[&[Fp]]", "extension_trace_lde_cols: Option<&[&[Fq]]>"]
-    if os.path.isdir("/root/reference"):                                 # ... which is eval_cpu::eval's, word for word
-        ref = open("/root/reference/src/eval_cpu.rs").read()
-        rsig = re.search(r"pub fn eval<Fp: GpuFftField<FftField = Fp> \+ FftField, Fq: StarkExtensionOf<Fp>>\((.*?)\) -> Matrix<Fq>", ref, re.S).group(1)
-        assert [p.strip() for p in rsig.strip().rstrip(",").split(",\n")] == params
+    assert _reference_targets()["eval_cpu_eval_params"] == params       # ... which is eval_cpu::eval's, word for word
     assert {"src_air.rs.patch", "src_lib.rs.patch", "src_composer.rs.patch"} <= set(os.listdir(os.path.join(ROOT, "rust", "patches")))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference tree is only present in the build container")
-def test_patches_apply_to_the_reference(tmp_path):
-    import shutil
-    import subprocess
+def _reference_targets():
+    """tests/golden/reference_patch_targets.json (scripts/gen_reference_patch_targets.py, run on a reference checkout)."""
+    import json
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "reference_patch_targets.json")))
+
+
+def test_patches_apply_to_the_reference():
+    """Every patch is a well-formed one-file unified diff, and every hunk's pre-image (context + removed lines) is, in order, a run of
+    lines of the reference file it patches: the SHA-256 of those lines recorded in the fixture."""
+    import hashlib
     pdir = os.path.join(ROOT, "rust", "patches")
     patches = sorted(f for f in os.listdir(pdir) if f.endswith(".patch"))
     assert {"src_matrix.rs.patch", "src_merkle.rs.patch", "src_fri.rs.patch", "gpu_src_lib.rs.patch", "gpu_src_prelude.rs.patch"} <= set(patches)
+    targets = _reference_targets()["patches"]
+    assert set(targets) == set(patches)
     for f in patches:
         text = open(os.path.join(pdir, f)).read()
-        rel = re.match(r"--- a/(\S+)", text).group(1)
-        dst = tmp_path / rel
-        dst.parent.mkdir(parents=True, exist_ok=True)
-        shutil.copy(os.path.join("/root/reference", rel), dst)
-        r = subprocess.run(["patch", "-p1", "--dry-run", "-i", os.path.join(pdir, f)], cwd=tmp_path, capture_output=True, text=True)
-        assert r.returncode == 0, f"{f}: {r.stdout}{r.stderr}"
+        assert len(re.findall(r"^--- a/", text, re.M)) == 1, f
+        rel = re.match(r"--- a/(\S+)\n\+\+\+ b/(\S+)\n", text)
+        assert rel and rel.group(1) == rel.group(2) == targets[f]["file"], f
+        hunks = []
+        for m in re.finditer(r"^@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@.*\n((?:[ +\\-].*\n|\n)*)", text, re.M):
+            body = [ln for ln in m.group(5).split("\n")[:-1] if not ln.startswith("\\")]
+            old = [ln[1:] for ln in body if ln[:1] in (" ", "-", "")]
+            new = [ln[1:] for ln in body if ln[:1] in (" ", "+", "")]
+            assert len(old) == int(m.group(2) or 1) and len(new) == int(m.group(4) or 1), f"{f}: hunk at line {m.group(1)} miscounted"
+            hunks.append(old)
+        want = targets[f]["hunks"]
+        assert len(hunks) == len(want), f
+        end = 0
+        for old, h in zip(hunks, want):
+            assert len(old) == h["lines"] and hashlib.sha256("\n".join(old).encode()).hexdigest() == h["sha256"], \
+                f"{f}: the hunk at line {h['line']} no longer matches {targets[f]['file']}"
+            assert h["line"] > end, f
+            end = h["line"] + h["lines"] - 1
