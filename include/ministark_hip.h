@@ -237,6 +237,24 @@ int ms_eval_program_ex(ms_ctx* ctx, const uint32_t* h_prog, unsigned ninstr, con
                        const void* const* d_periodic, const unsigned* periodic_len, unsigned nperiodic,
                        int out_field, void* d_out, unsigned flags);
 
+/* ---- constraint validation on the trace domain: Stark::validate_constraints (src/stark.rs:66-75, src/debug.rs:10-127;
+ * default_prove calls it under debug_assertions, src/prover.rs:75).  Program: public opcodes only; STORE_P / STORE_Q carry
+ * b = constraint index (< nconstraints; each index stored at most once; STORE_Q requires base_field = MS_GOLDILOCKS_FP).
+ * Domain: the 2^log_n-point trace subgroup, natural order; Trace(col, off) reads row (i + off) mod n.  The program runs as
+ * given (no rewriting pass, no specialised kernel) under Constraint::check's semantics (src/constraints.rs:172-248), with
+ * None for None: NEG, ADD, POW (every exponent, 0 included) and EMBED of None are None; MUL of None and a defined zero is 0, of None and
+ * anything else None; INV(None) = INV(0) = None (an Fq3 element is zero when all three components are).  Div(a, b) = MUL(a, INV(b))
+ * reproduces check's Div except for one arm: the reference gives Div(None, 0) = 0, a program gives None (the row is reported).
+ * Constraint c fails at row i when its stored value is None; h_first_row[c] = the first such row, UINT64_MAX when constraint
+ * c holds on every row, h_rows_failed[c] = how many rows fail.  MS_ERR_INVALID on any malformed input (unknown base field,
+ * out-of-range operand or store index, a Q op with the 252-bit field, null tables, more than 96 columns of a kind or 16
+ * periodic columns, nconstraints = 0).  Blocks. */
+int ms_validate_constraints(ms_ctx* ctx, int base_field, const uint32_t* h_prog, unsigned ninstr,
+                            const void* h_consts, unsigned nconst_words, unsigned log_n,
+                            const void* const* d_base_cols, unsigned nbase, const void* const* d_ext_cols, unsigned next,
+                            const void* const* d_periodic, const unsigned* periodic_len, unsigned nperiodic,
+                            unsigned nconstraints, uint64_t* h_first_row, uint64_t* h_rows_failed);
+
 /* Diagnostics: compile the specialised kernel for a (validated-shape) program without launching it;
  * needs no device.  *code_bytes receives the size of the gfx950 code object; on failure returns
  * MS_ERR_UNSUPPORTED with the compiler log in ms_last_error(). */

@@ -75,6 +75,7 @@ class Lib:
             "ms_sum_columns": (i, [vp, i, sz, c_void_pp, u, vp]),
             "ms_eval_program": (i, [vp, vp, u, vp, u, u, u, vp, vp, c_void_pp, u, c_void_pp, u, c_void_pp, vp, u, i, vp]),
             "ms_eval_program_ex": (i, [vp, vp, u, vp, u, u, u, vp, vp, c_void_pp, u, c_void_pp, u, c_void_pp, vp, u, i, vp, u]),
+            "ms_validate_constraints": (i, [vp, i, vp, u, vp, u, u, c_void_pp, u, c_void_pp, u, c_void_pp, vp, u, u, vp, vp]),
             "ms_eval_jit_check": (i, [vp, u, i, vp]),
             "ms_eval_jit_stats": (i, [vp, ctypes.POINTER(JitStats)]),
             "ms_scan_affine": (i, [vp, i, sz, vp, vp, vp, i, vp]),
