@@ -86,7 +86,7 @@ MS_HD uint64_t sub_lazy(uint64_t u, uint64_t t) {
 // weak -> canonical.  Deliberately a 64-bit compare, NOT "carry-out of x + EPS": with the
 // limb form hipcc (ROCm 7.2) folds addc(hi, 0, c) into the addition that produced `hi` and
 // then uses the carry-out of the merged three-input add -- a wrong value whenever `hi` itself
-// had wrapped (found by scripts/dbg_bfly.hip, device != host on the same source).
+// had wrapped (device != host on the same source; tests/test_field_primitives.py compares the two builds word for word).
 MS_HD uint64_t canon(uint64_t x) { return x >= gl::P ? x + gl::EPS : x; }
 
 // x * 2^S mod p for the in-network twiddles, S in {12,24,...,84}; canonical result.
