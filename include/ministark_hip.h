@@ -383,6 +383,26 @@ int ms_rpo256_rows_row_major(ms_ctx* ctx, size_t nrows, unsigned ncols, const vo
 int ms_rpo256_rows_field(ms_ctx* ctx, int field, size_t nrows, const void* const* d_cols, unsigned ncols, void* d_digests);
 int ms_rpo256_merkle(ms_ctx* ctx, size_t nleaves, const void* d_leaves, void* d_nodes);
 
+/* ---- BLAKE2s-256 commitments and proof-of-work: the fast H of MatrixMerkleTreeImpl<H> / PublicCoinImpl<F, H>
+ * (src/hash.rs:9-41 HashFn / ElementHashFn, src/merkle.rs:296-361, src/random.rs:61-141), opt-in; the SHA-256 entry points
+ * above stay the default.  H = unkeyed BLAKE2s, 32-byte digest (blake2::Blake2s256, Python's hashlib.blake2s: no key, salt
+ * or personalisation).  Digests are the 32 raw output bytes.  Each entry point is shaped like its SHA-256 twin:
+ * ms_blake2s_rows            leaves[r] = H( ||_c canonical little-endian bytes of d_cols[c][r] ): the bytes ms_sha256_rows
+ *                            hashes (ElementHashFn::hash_elements: Fp 8 bytes, Fq3 c0||c1||c2, Fp252 32 bytes).  A row of L
+ *                            bytes is ceil(L/64) blocks, the last zero-padded with counter L and the final flag; L = 0 (no
+ *                            columns) is H(""), one zero block.  ncols <= 128, else MS_ERR_UNSUPPORTED.
+ * ms_blake2s_rows_row_major  the same for a row-major matrix [nrows][ncols] (the FRI layer commitment, src/fri.rs:213-216);
+ *                            1 <= ncols <= 128.
+ * ms_blake2s_merkle          nodes[k] = H(nodes[2k] || nodes[2k+1]) (one 64-byte block), leaf pairs feed nodes[nleaves/2 ..),
+ *                            nodes[1] = root, nodes[0] = zero.  nleaves = 2^k >= 2.
+ * ms_blake2s_pow_grind       *nonce = the smallest n >= 1 such that H(seed32 || n as 8 big-endian bytes) has at least `bits`
+ *                            leading zero bits, byte 0's high bit first (merge_with_int + leading_zeros, src/random.rs:180-192).
+ *                            Blocks.  MS_ERR_INVALID if bits > 64 or no nonce exists below max_nonce. */
+int ms_blake2s_rows(ms_ctx* ctx, int field, size_t nrows, const void* const* d_cols, unsigned ncols, void* d_leaves);
+int ms_blake2s_rows_row_major(ms_ctx* ctx, int field, size_t nrows, unsigned ncols, const void* d_matrix, void* d_leaves);
+int ms_blake2s_merkle(ms_ctx* ctx, size_t nleaves, const void* d_leaves, void* d_nodes);
+int ms_blake2s_pow_grind(ms_ctx* ctx, const void* h_seed32, unsigned bits, uint64_t max_nonce, uint64_t* nonce);
+
 /* ---- multi-GPU exchange (new work: the reference has one metal::Device,
  * gpu/src/plan.rs:465-468).  One context per process and GPU; RCCL (librccl.so.1, loaded on first use)
  * over xGMI.  Transforms need no communication -- rank g owns the columns {c : c mod nranks == g}, in that

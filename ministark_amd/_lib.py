@@ -95,6 +95,10 @@ class Lib:
             "ms_rpo256_rows_row_major": (i, [vp, sz, u, vp, vp]),
             "ms_rpo256_merkle": (i, [vp, sz, vp, vp]),
             "ms_rpo256_rows_field": (i, [vp, i, sz, c_void_pp, u, vp]),
+            "ms_blake2s_rows": (i, [vp, i, sz, c_void_pp, u, vp]),
+            "ms_blake2s_rows_row_major": (i, [vp, i, sz, u, vp, vp]),
+            "ms_blake2s_merkle": (i, [vp, sz, vp, vp]),
+            "ms_blake2s_pow_grind": (i, [vp, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
             "ms_comm_unique_id": (i, [vp]),
             "ms_comm_init": (i, [vp, i, i, vp]),
             "ms_comm_destroy": (i, [vp]),

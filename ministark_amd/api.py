@@ -273,7 +273,7 @@ def _gather_digests(planner, digests, ndigests, ids):
     return _gather_digests_launch(planner, digests, ndigests, ids)()
 
 
-HASHES = ("sha256", "rpo256")
+HASHES = ("sha256", "rpo256", "blake2s")
 
 
 def merkle_view_ids(n, indices, lib=None):
@@ -346,7 +346,9 @@ class MerkleTree:
       "sha256"  Sha256HashFn (src/hash.rs:58-100), the reference's default;
       "rpo256"  RPO-256 over Goldilocks, the GPU-friendly commitment the reference prepared kernels for
                 (gpu/src/plan.rs:32-174, README.md:90): leaves by ms_rpo256_rows_field, nodes by
-                gen_rpo_merkle_tree.  A digest is 4 Fp elements = 32 bytes, so proofs have the same shape."""
+                gen_rpo_merkle_tree.  A digest is 4 Fp elements = 32 bytes, so proofs have the same shape;
+      "blake2s" BLAKE2s-256 (blake2::Blake2s256, hashlib.blake2s): the leaves hash the bytes SHA-256 hashes, a merge is one
+                compression instead of two.  Any of the three fields."""
 
     def __init__(self, planner, leaves, nleaves, hash="sha256"):
         if hash not in HASHES:
@@ -359,6 +361,8 @@ class MerkleTree:
         L = planner.lib
         if hash == "sha256":
             L.check(L.ms_sha256_merkle(planner.handle, nleaves, leaves.ptr, self.nodes.ptr))
+        elif hash == "blake2s":
+            L.check(L.ms_blake2s_merkle(planner.handle, nleaves, leaves.ptr, self.nodes.ptr))
         else:
             L.check(L.ms_rpo256_merkle(planner.handle, nleaves, leaves.ptr, self.nodes.ptr))
 
@@ -380,6 +384,8 @@ class MerkleTree:
                 raise ValueError("RPO-256 absorbs Goldilocks elements")
             words = folding_factor * FIELD_WORDS[evaluations.field]          # a row is N elements = N (or 3 N) Fp words in memory order
             pl.lib.check(pl.lib.ms_rpo256_rows_row_major(pl.handle, nrows, words, evaluations.ptr, leaves.ptr))
+        elif hash == "blake2s":
+            pl.lib.check(pl.lib.ms_blake2s_rows_row_major(pl.handle, evaluations.field, nrows, folding_factor, evaluations.ptr, leaves.ptr))
         else:
             raise ValueError(f"unknown hash {hash!r} (one of {HASHES})")
         return cls(pl, leaves, nrows, hash)
@@ -712,7 +718,7 @@ class Matrix:
 
     def hash_rows(self, hash="sha256"):
         """`hash_rows::<F, H>` (src/merkle.rs:412-436, src/matrix.rs:254-280): one digest per row ->
-        DeviceBytes of num_rows x 32.  H = Sha256HashFn ("sha256") or RPO-256 ("rpo256", Goldilocks columns)."""
+        DeviceBytes of num_rows x 32.  H = Sha256HashFn ("sha256"), RPO-256 ("rpo256", Goldilocks columns) or BLAKE2s-256 ("blake2s")."""
         pl = self.planner
         n = self.num_rows()
         leaves = DeviceBytes(pl, n * 32)
@@ -720,6 +726,8 @@ class Matrix:
             pl.lib.check(pl.lib.ms_sha256_rows(pl.handle, self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr))
         elif hash == "rpo256":
             pl.lib.check(pl.lib.ms_rpo256_rows_field(pl.handle, self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr))
+        elif hash == "blake2s":
+            pl.lib.check(pl.lib.ms_blake2s_rows(pl.handle, self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr))
         else:
             raise ValueError(f"unknown hash {hash!r} (one of {HASHES})")
         return leaves
@@ -864,12 +872,21 @@ def gen_rpo_merkle_tree(leaves):
     return nodes
 
 
-def grind_proof_of_work(planner, seed, proof_of_work_bits, max_nonce=(1 << 40)):
+def pow_hash(commitment_hash):
+    """The proof-of-work hash of a prover that commits with `commitment_hash`: BLAKE2s grinds with BLAKE2s; SHA-256 and RPO-256
+    provers grind with SHA-256, as they always have."""
+    return "blake2s" if commitment_hash == "blake2s" else "sha256"
+
+
+def grind_proof_of_work(planner, seed, proof_of_work_bits, max_nonce=(1 << 40), hash="sha256"):
     """`PublicCoin::grind_proof_of_work(bits)` (src/random.rs:48-55): the smallest nonce >= 1 whose
-    SHA-256(seed || nonce_be) has `bits` leading zero bits.  seed: 32 bytes."""
+    H(seed || nonce_be) has `bits` leading zero bits.  seed: 32 bytes.  H = SHA-256 ("sha256") or BLAKE2s-256 ("blake2s")."""
     seed = bytes(seed)
     assert len(seed) == 32
+    if hash not in ("sha256", "blake2s"):
+        raise ValueError(f"unknown proof-of-work hash {hash!r} (sha256 or blake2s)")
     out = ctypes.c_uint64(0)
     buf = ctypes.create_string_buffer(seed, 32)
-    planner.lib.check(planner.lib.ms_sha256_pow_grind(planner.handle, buf, proof_of_work_bits, max_nonce, ctypes.byref(out)))
+    grind = planner.lib.ms_blake2s_pow_grind if hash == "blake2s" else planner.lib.ms_sha256_pow_grind
+    planner.lib.check(grind(planner.handle, buf, proof_of_work_bits, max_nonce, ctypes.byref(out)))
     return out.value

@@ -301,9 +301,10 @@ public:
     std::vector<void*> ptrs() const { std::vector<void*> p; for (auto& c : columns) p.push_back(c.ptr()); return p; }
 };
 
-// H of MatrixMerkleTreeImpl<H> (src/merkle.rs:296-361): Sha256HashFn (src/hash.rs:58-100) or RPO-256 over
-// Goldilocks (gpu/src/plan.rs:32-174, README.md:90).  Both digests are 32 bytes, proofs have the same shape.
-enum class Hash { Sha256, Rpo256 };
+// H of MatrixMerkleTreeImpl<H> (src/merkle.rs:296-361): Sha256HashFn (src/hash.rs:58-100), RPO-256 over
+// Goldilocks (gpu/src/plan.rs:32-174, README.md:90) or BLAKE2s-256 (any field; the bytes SHA-256 hashes, one compression per
+// merge).  All digests are 32 bytes, proofs have the same shape.
+enum class Hash { Sha256, Rpo256, Blake2s };
 
 class MerkleTree {
 public:
@@ -312,6 +313,7 @@ public:
         MerkleTree t(m.planner(), m.num_rows());
         std::vector<const void*> in; for (auto& c : m.columns) in.push_back(c.ptr());
         if (h == Hash::Sha256) check(ms_sha256_rows(t.pl_->ctx(), F::id, t.n_, in.data(), (unsigned)in.size(), t.leaves_));
+        else if (h == Hash::Blake2s) check(ms_blake2s_rows(t.pl_->ctx(), F::id, t.n_, in.data(), (unsigned)in.size(), t.leaves_));
         else check(ms_rpo256_rows_field(t.pl_->ctx(), F::id, t.n_, in.data(), (unsigned)in.size(), t.leaves_));
         t.build(h);
         return t;
@@ -322,6 +324,7 @@ public:
     static MerkleTree from_fri_layer(const GpuVec<F>& evaluations, unsigned folding_factor, Hash h = Hash::Sha256) {
         MerkleTree t(evaluations.planner(), evaluations.len() / folding_factor);
         if (h == Hash::Sha256) check(ms_sha256_rows_row_major(t.pl_->ctx(), F::id, t.n_, folding_factor, evaluations.ptr(), t.leaves_));
+        else if (h == Hash::Blake2s) check(ms_blake2s_rows_row_major(t.pl_->ctx(), F::id, t.n_, folding_factor, evaluations.ptr(), t.leaves_));
         else check(ms_rpo256_rows_row_major(t.pl_->ctx(), t.n_, folding_factor * (unsigned)(ms_field_bytes(F::id) / 8), evaluations.ptr(), t.leaves_));
         t.build(h);
         return t;
@@ -381,6 +384,7 @@ private:
     MerkleTree(Planner& pl, size_t n) : pl_(&pl), n_(n) { check(ms_alloc(pl.ctx(), n * 32, &leaves_)); check(ms_alloc(pl.ctx(), n * 32, &nodes_)); }
     void build(Hash h) {
         if (h == Hash::Sha256) check(ms_sha256_merkle(pl_->ctx(), n_, leaves_, nodes_));
+        else if (h == Hash::Blake2s) check(ms_blake2s_merkle(pl_->ctx(), n_, leaves_, nodes_));
         else check(ms_rpo256_merkle(pl_->ctx(), n_, leaves_, nodes_));
     }
     Pending gather_launch(const void* digests, const std::vector<uint64_t>& ids, GatherArena* arena) const {

@@ -127,10 +127,13 @@ private:
     bool has_ext_tree_, has_ext_lde_, fetched_ = false;
 };
 
-// PublicCoin::grind_proof_of_work(bits): the smallest nonce >= 1 with `bits` leading zero bits of SHA-256(seed || nonce_be)
-inline uint64_t grind_proof_of_work(Planner& pl, const std::array<uint8_t, 32>& seed, unsigned proof_of_work_bits, uint64_t max_nonce = (uint64_t)1 << 40) {
+// PublicCoin::grind_proof_of_work(bits): the smallest nonce >= 1 with `bits` leading zero bits of H(seed || nonce_be),
+// H = SHA-256 (Hash::Sha256, also what an RPO-256 prover grinds with) or BLAKE2s-256 (Hash::Blake2s)
+inline uint64_t grind_proof_of_work(Planner& pl, const std::array<uint8_t, 32>& seed, unsigned proof_of_work_bits, uint64_t max_nonce = (uint64_t)1 << 40,
+                                    Hash h = Hash::Sha256) {
     uint64_t nonce = 0;
-    check(ms_sha256_pow_grind(pl.ctx(), seed.data(), proof_of_work_bits, max_nonce, &nonce));
+    if (h == Hash::Blake2s) check(ms_blake2s_pow_grind(pl.ctx(), seed.data(), proof_of_work_bits, max_nonce, &nonce));
+    else check(ms_sha256_pow_grind(pl.ctx(), seed.data(), proof_of_work_bits, max_nonce, &nonce));
     return nonce;
 }
 

@@ -473,7 +473,7 @@ def prove_sharded(planner, comm, local_cols, total_cols, log_rows, comp_expr, dr
     prover.  See the placement table above.  phases_ms: a dict that receives this rank's wall time per phase (a device sync each)."""
     import time
     from . import expr as E
-    from .api import Radix2EvaluationDomain, apply_drp, gl_to_mont, grind_proof_of_work, _offset_words
+    from .api import Radix2EvaluationDomain, apply_drp, gl_to_mont, grind_proof_of_work, pow_hash, _offset_words
     from .composer import DeepPolyComposer
     from .pipeline import _lowered, fold_positions
     pl, L, G, r = planner, planner.lib, comm.world, comm.rank
@@ -617,7 +617,7 @@ def prove_sharded(planner, comm, local_cols, total_cols, log_rows, comp_expr, dr
     if r == 0:
         rem = Matrix([cur.clone()]).bit_reverse_rows().into_polynomials(Radix2EvaluationDomain(n)).columns[0]
         out["remainder_coeffs"] = rem.to_numpy()[: max(n // blowup, 1)]
-        out["nonce"] = grind_proof_of_work(pl, roots[-1] if roots else out["composition_root"], grinding_bits)
+        out["nonce"] = grind_proof_of_work(pl, roots[-1] if roots else out["composition_root"], grinding_bits, hash=pow_hash(hash))
     lap("remainder + proof of work")
     positions = [int(p) for p in draws.positions]
     if G == 1:

@@ -27,7 +27,7 @@ import numpy as np
 
 from . import expr as E
 from .api import (GL_P, GOLDILOCKS_FP, Matrix, MerkleTree, Queries, Radix2EvaluationDomain, apply_drp, gl_to_mont,
-                  grind_proof_of_work)
+                  grind_proof_of_work, pow_hash)
 from .composer import DeepCompositionCoeffs, DeepPolyComposer
 
 
@@ -297,7 +297,8 @@ def prove_phases(planner, trace, comp_expr, draws, blowup=4, folding=8, max_rema
         fine[name] = round((now - tf) * 1e3, 3)
         tf = now
 
-    out["nonce"] = grind_proof_of_work(pl, roots[-1] if roots else out["composition_root"], grinding_bits)   # prover.rs:160
+    out["nonce"] = grind_proof_of_work(pl, roots[-1] if roots else out["composition_root"], grinding_bits,   # prover.rs:160
+                                       hash=pow_hash(hash))
     sub("proof of work")
     from .api import GatherBatch
     batch = GatherBatch(pl)                                                    # every gather of the phase into one buffer: ONE download
