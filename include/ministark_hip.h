@@ -322,7 +322,8 @@ int ms_fri_fold(ms_ctx* ctx, int field, unsigned log_n, unsigned folding_factor,
                 const void* h_offset, const void* d_evals, void* d_out);
 /* ms_fri_fold_rows: the same fold on a ROW SHARD of the layer -- chunks [first_chunk, first_chunk + nchunks) of the 2^log_n /
  * folding_factor chunks; d_evals holds those nchunks * folding_factor evaluations, d_out receives nchunks.  (A chunk folds from its own
- * values and its position alone: the multi-GPU FRI prover keeps every layer sharded by rows and folds without communication.) */
+ * values and its position alone: the multi-GPU FRI prover keeps every layer sharded by rows and folds without communication.)
+ * All three fields; the shards' outputs concatenate to ms_fri_fold's words. */
 int ms_fri_fold_rows(ms_ctx* ctx, int field, unsigned log_n, unsigned folding_factor, const void* h_alpha,
                      const void* h_offset, size_t first_chunk, size_t nchunks, const void* d_evals, void* d_out);
 
@@ -346,7 +347,10 @@ int ms_fri_fold_rows(ms_ctx* ctx, int field, unsigned log_n, unsigned folding_fa
  *                  (src/prover.rs:149-152) without forming the coefficients -- the quotient is a polynomial, so its values
  *                  at the LDE points are these, bit for bit.  With first = 0, count = 2^log_domain one GPU's whole first FRI
  *                  layer; with a row shard (rank r of G: first = r 2^log_domain / G) the multi-GPU form, no communication.
- *                  Goldilocks fields.  Asynchronous. */
+ *                  MS_STARK252_FP: every column is a base column (next must be 0, MS_ERR_INVALID otherwise), points / alphas /
+ *                  values are 4 Montgomery words each, h_offset NULL = the field's generator 3.  A point that lies on the LDE
+ *                  coset, a zero or non-canonical offset, rows outside the domain: MS_ERR_INVALID, nothing written.  The words
+ *                  do not depend on how the domain is split into calls.  Asynchronous. */
 int ms_horner_eval(ms_ctx* ctx, int coeff_field, int point_field, size_t n, const void* const* d_cols, unsigned ncols,
                    const unsigned* h_qcol, const void* h_qpoints, unsigned nq, void* h_out);
 int ms_deep_rows(ms_ctx* ctx, int point_field, unsigned log_domain, const void* h_offset, size_t first, size_t count,

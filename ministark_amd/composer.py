@@ -197,11 +197,9 @@ class DeepPolyComposer:
     def into_deep_evaluations(self, coeffs, base_lde, ext_lde, comp_lde, domain_size, first=0, offset=None):
         """`into_deep_poly(coeffs)` followed by `into_bit_reversed_evaluations(lde_domain)` (src/prover.rs:149-152) in one step and
         without the transforms: the composition polynomial's values at rows [first, first + count) of the bit-reversed LDE domain
-        (domain_size points, coset offset `offset`, default 7), computed from those rows of the committed LDE matrices -- the same
+        (domain_size points, coset offset `offset`, default the field's generator: 7, or 3 over the 252-bit field), computed from those rows of the committed LDE matrices -- the same
         field elements (the quotient is a polynomial).  The matrices hold `count` rows: the whole domain on one GPU, or a rank's
         row shard (ministark_amd.distributed.prove_sharded)."""
-        if self.base_field == STARK252_FP:
-            raise ValueError("into_deep_evaluations: Goldilocks fields")
         count = base_lde.num_rows()
         ext_cols = list(ext_lde.columns) if ext_lde is not None else []
         for m in ([base_lde, comp_lde] + ([ext_lde] if ext_lde is not None else [])):
@@ -210,6 +208,7 @@ class DeepPolyComposer:
         off = None
         if offset is not None:
             from .api import _offset_words
-            off = _offset_words(GOLDILOCKS_FP, offset)          # (kept alive by head_args until the call has returned)
+            fft_field = STARK252_FP if self.base_field == STARK252_FP else GOLDILOCKS_FP
+            off = _offset_words(fft_field, offset)              # (kept alive by head_args until the call has returned)
         return self._compose(self.planner.lib.ms_deep_rows, (domain_size.bit_length() - 1, off, first, count), coeffs, base_lde.columns,
                              ext_cols, comp_lde.columns, GpuVec(self.planner, count, self.fq))

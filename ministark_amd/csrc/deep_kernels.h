@@ -471,4 +471,131 @@ static __global__ void __launch_bounds__(NT) deep_degree_adjust(uint64_t* dst, c
     st(dst, i, f252::add(f252::mul(c, alpha), f252::mul(prev, beta)));
 }
 
+// ms_deep_rows over the 252-bit field: the value of
+//     (adj_alpha + adj_beta x) sum_k 1/(x - z_k) (sum_{t: pt = k} alpha_t P_ct(x)  -  csum_k)
+// at rows [first, first + n) of the bit-reversed LDE domain, from those rows of the committed LDE columns.
+struct RowsParams {
+    const uint64_t* cols[msdeep::MAXCOLS];   // the n rows of every LDE column
+    const Term* terms;                       // device, sorted by point
+    const uint64_t* tw_lo;                   // w_N^i two-level table of a forward 252 plan of the LDE domain's size
+    const uint64_t* tw_hi;
+    uint64_t points[msdeep::MAXPOINTS][4];
+    uint64_t csum[msdeep::MAXPOINTS][4];     // sum_{t: pt = k} alpha_t ood_t (host)
+    uint64_t h[4];                           // coset offset
+    uint64_t adj_alpha[4], adj_beta[4];
+    uint64_t* out;
+    size_t n, first;
+    unsigned npoints, lo_bits, log_dom;
+    unsigned term_start[msdeep::MAXPOINTS + 1];
+};
+__device__ __forceinline__ E rows_x(const RowsParams& P, size_t row) {
+    const size_t nat = (size_t)(__brevll((unsigned long long)(P.first + row)) >> (64 - P.log_dom));
+    E x = ld(P.tw_lo, nat & (((size_t)1 << P.lo_bits) - 1));
+    if (nat >> P.lo_bits) x = f252::mul(x, ld(P.tw_hi, nat >> P.lo_bits));
+    return f252::mul(x, E{{P.h[0], P.h[1], P.h[2], P.h[3]}});
+}
+__device__ __forceinline__ E rows_point(const RowsParams& P, unsigned k) { return {{P.points[k][0], P.points[k][1], P.points[k][2], P.points[k][3]}}; }
+// An inversion here is a Fermat power of ~250 squarings (f252::inv): two hundred times a term.  It is shared three ways (Montgomery's
+// trick each time; exact arithmetic, so the words do not depend on the grouping):
+//   * a row's npoints denominators x - z_k are multiplied up into one value r before anything is inverted;
+//   * a lane chains its R rows (rows i, i + 64 WAVES, ...: coalesced), the prefix of each row parked in LDS;
+//   * lane l of ONE wave multiplies the WAVES waves' lane-l chains, inverts, and hands every wave its own inverse back.
+// One wave-wide inversion serves 64 R WAVES rows.  Coming back, a row has 1/r; the factor of point k is (1/r) prod_{i != k} (x - z_i),
+// formed when the point's terms are summed -- npoints (npoints - 1) products and no per-point array (three points: six).  A point's
+// terms alpha_t P_ct(x) accumulate UNREDUCED in the nine-digit columns of f252::mac81, sixteen to one Montgomery reduction.
+static constexpr int ROWS_PER_LANE = 4, ROWS_WAVES = 4;   // the shipped shape: 1024 rows per workgroup, 16 per inverted value
+template <int R, int WAVES>
+__global__ void __launch_bounds__(64 * WAVES) deep_rows(RowsParams P) {
+    constexpr int NT = 64 * WAVES;
+    static_assert(WAVES == 4 || WAVES == 8, "the inverting wave is blockIdx.x & (WAVES - 1)");
+    __shared__ uint64_t pre[(R > 1 ? R - 1 : 1) * 4 * NT];   // prefix products of rows 1 .. R-1, word-major: [j - 1][word][thread] (R = 1: unused)
+    __shared__ uint64_t pool[4 * NT];                   // a wave's chains going in, their inverses coming out: [wave][word][lane]
+    __shared__ uint64_t part[(WAVES - 1) * 4 * 64];     // the inverting wave's partial products a_0 .. a_v, v < WAVES - 1
+    const unsigned tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const size_t i0 = (size_t)blockIdx.x * (NT * R) + tid;
+    // a lane past the end works on row 0 of the shard (a denominator that cannot vanish) and stores nothing
+    auto row_of = [&](int j) { const size_t i = i0 + (size_t)j * NT; return i < P.n ? i : (size_t)0; };
+    auto row_product = [&](const E& x) {
+        E r = f252::sub(x, rows_point(P, 0));
+        for (unsigned k = 1; k < P.npoints; k++) r = f252::mul(r, f252::sub(x, rows_point(P, k)));
+        return r;
+    };
+    // x is formed twice, here and on the way back (two products of a row's forty): R values held across the inversion would cost the
+    // registers of a fourth wave per SIMD, or as much LDS again as the prefixes take.  Both row loops stay loops: a quarter of the code.
+    E run = f252::one();
+    #pragma unroll 1
+    for (int j = 0; j < R; j++) {
+        const E r = row_product(rows_x(P, row_of(j)));
+        if (j == 0) run = r;
+        else {
+            #pragma unroll
+            for (int w = 0; w < 4; w++) pre[((j - 1) * 4 + w) * NT + tid] = run.l[w];
+            run = f252::mul(run, r);
+        }
+    }
+    #pragma unroll
+    for (int w = 0; w < 4; w++) pool[(wv * 4 + w) * 64 + lane] = run.l[w];
+    __syncthreads();
+    if (wv == (blockIdx.x & (WAVES - 1))) {                  // the inverting wave rotates with the workgroup
+        auto get = [&](int v) { return E{{pool[(v * 4) * 64 + lane], pool[(v * 4 + 1) * 64 + lane], pool[(v * 4 + 2) * 64 + lane], pool[(v * 4 + 3) * 64 + lane]}}; };
+        E all = get(0);
+        #pragma unroll 1
+        for (int v = 1; v < WAVES; v++) {                    // part[v - 1] = a_0 .. a_(v-1)
+            #pragma unroll
+            for (int w = 0; w < 4; w++) part[((v - 1) * 4 + w) * 64 + lane] = all.l[w];
+            all = f252::mul(all, get(v));
+        }
+        E t = f252::inv(all);                                // 1 / (a_0 .. a_(WAVES-1))
+        #pragma unroll 1
+        for (int v = WAVES - 1; v >= 0; v--) {
+            E r = t;                                         // 1 / a_v = t a_0 .. a_(v-1)
+            if (v) {
+                r = f252::mul(t, E{{part[((v - 1) * 4) * 64 + lane], part[((v - 1) * 4 + 1) * 64 + lane], part[((v - 1) * 4 + 2) * 64 + lane], part[((v - 1) * 4 + 3) * 64 + lane]}});
+                t = f252::mul(t, get(v));
+            }
+            #pragma unroll
+            for (int w = 0; w < 4; w++) pool[(v * 4 + w) * 64 + lane] = r.l[w];
+        }
+    }
+    __syncthreads();
+    E inv = {{pool[(wv * 4) * 64 + lane], pool[(wv * 4 + 1) * 64 + lane], pool[(wv * 4 + 2) * 64 + lane], pool[(wv * 4 + 3) * 64 + lane]}};
+    #pragma unroll 1
+    for (int j = R - 1; j >= 0; j--) {
+        const size_t row = row_of(j);
+        const E x = rows_x(P, row);
+        E rinv = inv;                                        // 1 / r_j
+        if (j > 0) {
+            const E pj = {{pre[((j - 1) * 4) * NT + tid], pre[((j - 1) * 4 + 1) * NT + tid], pre[((j - 1) * 4 + 2) * NT + tid], pre[((j - 1) * 4 + 3) * NT + tid]}};
+            rinv = f252::mul(inv, pj);
+            inv = f252::mul(inv, row_product(x));
+        }
+        E acc = f252::zero();
+        for (unsigned k = 0; k < P.npoints; k++) {           // wave-uniform bounds, points and terms
+            E q = rinv;
+            for (unsigned i = 0; i < P.npoints; i++) if (i != k) q = f252::mul(q, f252::sub(x, rows_point(P, i)));
+            E sum = f252::zero();
+            for (unsigned t0 = P.term_start[k]; t0 < P.term_start[k + 1]; t0 += 16) {
+                const unsigned t1 = t0 + 16 < P.term_start[k + 1] ? t0 + 16 : P.term_start[k + 1];
+                uint64_t c[19];
+                #pragma unroll
+                for (int s = 0; s < 19; s++) c[s] = 0;
+                #pragma unroll 2
+                for (unsigned t = t0; t < t1; t++) {
+                    const Term& T = P.terms[t];
+                    uint32_t a[9], v[9];
+                    f252::digits9(E{{T.alpha[0], T.alpha[1], T.alpha[2], T.alpha[3]}}, a);
+                    f252::digits9(ld(P.cols[T.col], row), v);
+                    f252::mac81(c, v, a);
+                }
+                sum = f252::add(sum, f252::reduce_columns<true>(c));
+            }
+            sum = f252::sub(sum, E{{P.csum[k][0], P.csum[k][1], P.csum[k][2], P.csum[k][3]}});
+            acc = f252::add(acc, f252::mul(sum, q));
+        }
+        const E bx = f252::mul(E{{P.adj_beta[0], P.adj_beta[1], P.adj_beta[2], P.adj_beta[3]}}, x);
+        acc = f252::mul(acc, f252::add(E{{P.adj_alpha[0], P.adj_alpha[1], P.adj_alpha[2], P.adj_alpha[3]}}, bx));
+        if (i0 + (size_t)j * NT < P.n) st(P.out, i0 + (size_t)j * NT, acc);
+    }
+}
+
 }  // namespace msdeep252

@@ -116,13 +116,14 @@ struct Fold252Params {
     uint64_t hinv[4];           // h^-1
     uint64_t alpha[4];
     uint64_t zinv[8][4];        // (w_n^(-n/ff))^k, k < ff/2
+    size_t first_chunk, nchunks;   // ms_fri_fold_rows: src holds chunks [first_chunk, first_chunk + nchunks) of the layer, dst receives as many values
 };
 template <int FF>
 __global__ void __launch_bounds__(NT, 2) fri_fold252(Fold252Params P) {      // FF elements of 8 dwords live in registers
     constexpr int LOGF = FF == 2 ? 1 : FF == 4 ? 2 : FF == 8 ? 3 : 4;
-    const size_t c = (size_t)blockIdx.x * NT + threadIdx.x;
-    if (c >> P.log_m) return;
-    const size_t i = P.log_m ? (size_t)(__brevll((unsigned long long)c) >> (64 - P.log_m)) : 0;
+    const size_t c = (size_t)blockIdx.x * NT + threadIdx.x;       // chunk of the shard; its position in the layer decides x_i
+    if (c >= P.nchunks) return;
+    const size_t i = P.log_m ? (size_t)(__brevll((unsigned long long)(P.first_chunk + c)) >> (64 - P.log_m)) : 0;
     const f252::E xinv = f252::mul(pow2l(P.tw_lo, P.tw_hi, P.lo_bits, i), f252::E{{P.hinv[0], P.hinv[1], P.hinv[2], P.hinv[3]}});
     f252::E A[FF];
     #pragma clang loop unroll(full)

@@ -8,6 +8,12 @@
 // Host values of Fq are canonical integers: FqVal{c0,c1,c2} (c1 = c2 = 0 when Fq = Fp).
 #pragma once
 #include "ministark.hpp"
+#include <stdint.h>
+// host arithmetic of the 252-bit field (points and offsets of its composer): the library's own fp252.h, kept inside ms:: so that its
+// Goldilocks namespace does not meet ms::gl in a program that says `using namespace ms`
+namespace ms { namespace lib252 {
+#include "../fp252.h"
+} namespace f252 = lib252::f252; }
 
 namespace ms {
 
@@ -31,6 +37,12 @@ inline uint64_t from_mont(uint64_t m) { return gl::mul(m, gl::pow(0xFFFFFFFFull,
 template <class F> inline FqVal from_words(const uint64_t* w) { FqVal v; for (unsigned k = 0; k < F::words; k++) v.c[k] = from_mont(w[k]); return v; }
 }  // namespace fq
 
+// a domain offset (a small canonical integer) as the Montgomery words of F's FFT field: one word, or four for Fp252
+template <class F>
+inline std::array<uint64_t, 4> offset_words(uint64_t domain_offset) {
+    if constexpr (F::words == 4) { const f252::E m = f252::to_mont(f252::E{{domain_offset, 0, 0, 0}}); return {{m.l[0], m.l[1], m.l[2], m.l[3]}}; }
+    else return {{gl::to_mont(domain_offset), 0, 0, 0}};
+}
 // apply_drp(evals, domain_offset, alpha, folding_factor): `evals` in bit-reversed order; returns the next layer
 // (bit-reversed).  alpha: Montgomery words of one element of F.
 template <class F>
@@ -38,8 +50,21 @@ inline GpuVec<F> apply_drp(const GpuVec<F>& evals, const std::vector<uint64_t>& 
     if (alpha.size() != F::words) throw std::invalid_argument("alpha has the wrong number of limbs");
     GpuVec<F> out(evals.planner(), evals.len() / folding_factor);
     unsigned log_n = 0; while (((size_t)1 << log_n) < evals.len()) log_n++;
-    const uint64_t off = gl::to_mont(domain_offset);
-    check(ms_fri_fold(evals.planner().ctx(), F::id, log_n, folding_factor, alpha.data(), &off, evals.ptr(), out.ptr()));
+    const auto off = offset_words<F>(domain_offset);
+    check(ms_fri_fold(evals.planner().ctx(), F::id, log_n, folding_factor, alpha.data(), off.data(), evals.ptr(), out.ptr()));
+    return out;
+}
+// the same fold on a row shard of a layer of 2^log_n evaluations: `shard` holds chunks [first_chunk, first_chunk + shard.len() / folding_factor)
+// of the bit-reversed layer and the result is those chunks of the next one (ms_fri_fold_rows; Fp, Fq3 and Fp252)
+template <class F>
+inline GpuVec<F> apply_drp_rows(const GpuVec<F>& shard, const std::vector<uint64_t>& alpha, unsigned folding_factor, unsigned log_n, size_t first_chunk,
+                                uint64_t domain_offset = 1) {
+    if (alpha.size() != F::words) throw std::invalid_argument("alpha has the wrong number of limbs");
+    if (shard.len() % folding_factor) throw std::invalid_argument("apply_drp_rows: a shard holds whole chunks");
+    const size_t nchunks = shard.len() / folding_factor;
+    GpuVec<F> out(shard.planner(), nchunks);
+    const auto off = offset_words<F>(domain_offset);
+    check(ms_fri_fold_rows(shard.planner().ctx(), F::id, log_n, folding_factor, alpha.data(), off.data(), first_chunk, nchunks, shard.ptr(), out.ptr()));
     return out;
 }
 
@@ -171,6 +196,7 @@ public:
                 qp.insert(qp.end(), cp.begin(), cp.end());
                 const auto all = horner_cols<Fp>(base_.planner(), base_.num_rows(), cols, qc, qp);
                 bv.assign(all.begin(), all.begin() + bq_col.size()); cv.assign(all.begin() + bq_col.size(), all.end());
+                if (ext_) ev = horner(*ext_, eq_col, eq_pt);      // an Fq = Fp AIR may still carry extension columns (over Fp): their own launch
                 comp_done = true;
             }
         } else if (ext_ && comp_.num_rows() == ext_->num_rows() && ext_->num_cols() + comp_.num_cols() <= 96 && !eq_col.empty()) {
@@ -263,6 +289,93 @@ private:
     size_t n_; FqVal z_; const Matrix<Fp>& base_; const Matrix<FqT>* ext_; const Matrix<FqT>& comp_;
     uint64_t g_ = 1, g_inv_ = 1; unsigned nbase_ = 0;
     std::vector<FqVal> ood_exec_, ood_comp_; bool have_ood_ = false;
+};
+
+// ---- the composer over the 252-bit field (Fq = Fp = Fp252: no extension, every column a base column).  Host values are Montgomery
+// words (f252::E): what the C ABI takes and what f252:: multiplies.  Same methods as above; the LDE offset defaults to the field's generator 3.
+struct DeepCompositionCoeffs252 { std::vector<f252::E> execution_trace, composition_trace; f252::E degree[2]; };
+template <>
+class DeepPolyComposer<Fp252> {
+public:
+    DeepPolyComposer(std::vector<std::pair<unsigned, int>> trace_arguments, size_t trace_len, f252::E z, const Matrix<Fp252>& base_polys,
+                     const Matrix<Fp252>& composition_polys)
+        : args_(std::move(trace_arguments)), n_(trace_len), z_(z), base_(base_polys), comp_(composition_polys) {
+        unsigned log_n = 0; while (((size_t)1 << log_n) < trace_len) log_n++;
+        g_ = f252::root_of_unity(log_n); g_inv_ = f252::inv(g_);
+        nbase_ = (unsigned)base_.num_cols();
+    }
+    f252::E point(int offset) const { return f252::mul(z_, f252::pow_u64(offset >= 0 ? g_ : g_inv_, (uint64_t)(offset >= 0 ? offset : -offset))); }
+    f252::E composition_point() const { return f252::pow_u64(z_, comp_.num_cols()); }
+    std::pair<std::vector<f252::E>, std::vector<f252::E>> get_ood_evals() {
+        std::vector<const void*> cols;
+        for (auto& c : base_.columns) cols.push_back(c.ptr());
+        std::vector<unsigned> qc; std::vector<uint64_t> pts;
+        auto push = [&](unsigned col, const f252::E& p) { qc.push_back(col); pts.insert(pts.end(), p.l, p.l + 4); };
+        for (auto& a : args_) push(a.first, point(a.second));
+        const bool together = comp_.num_rows() == base_.num_rows() && base_.num_cols() + comp_.num_cols() <= 96;   // one launch, one download
+        std::vector<uint64_t> out((args_.size() + comp_.num_cols()) * 4);
+        if (together) {
+            for (auto& c : comp_.columns) cols.push_back(c.ptr());
+            for (unsigned c = 0; c < comp_.num_cols(); c++) push(nbase_ + c, composition_point());
+            check(ms_horner_eval(base_.planner().ctx(), Fp252::id, Fp252::id, base_.num_rows(), cols.data(), (unsigned)cols.size(), qc.data(), pts.data(), (unsigned)qc.size(), out.data()));
+        } else {
+            if (!qc.empty()) check(ms_horner_eval(base_.planner().ctx(), Fp252::id, Fp252::id, base_.num_rows(), cols.data(), (unsigned)cols.size(), qc.data(), pts.data(), (unsigned)qc.size(), out.data()));
+            std::vector<const void*> cc; std::vector<unsigned> cq; std::vector<uint64_t> cp;
+            const f252::E zn = composition_point();
+            for (unsigned c = 0; c < comp_.num_cols(); c++) { cc.push_back(comp_.columns[c].ptr()); cq.push_back(c); cp.insert(cp.end(), zn.l, zn.l + 4); }
+            check(ms_horner_eval(base_.planner().ctx(), Fp252::id, Fp252::id, comp_.num_rows(), cc.data(), (unsigned)cc.size(), cq.data(), cp.data(), (unsigned)cq.size(), out.data() + args_.size() * 4));
+        }
+        auto at = [&](size_t k) { f252::E e; memcpy(e.l, &out[4 * k], 32); return e; };
+        ood_exec_.clear(); ood_comp_.clear();
+        for (size_t k = 0; k < args_.size(); k++) ood_exec_.push_back(at(k));
+        for (size_t c = 0; c < comp_.num_cols(); c++) ood_comp_.push_back(at(args_.size() + c));
+        have_ood_ = true;
+        return {ood_exec_, ood_comp_};
+    }
+    GpuVec<Fp252> into_deep_poly(const DeepCompositionCoeffs252& coeffs) {
+        unsigned log_n = 0; while (((size_t)1 << log_n) < n_) log_n++;
+        return compose(coeffs, base_, comp_, n_, [&](Planner& pl, const std::vector<const void*>& cols, const Terms& t, void* out) {
+            return ms_deep_compose(pl.ctx(), Fp252::id, log_n, nullptr, cols.data(), (unsigned)cols.size(), nullptr, 0, t.pts.data(), t.npoints, t.tcol.data(), t.tpoint.data(),
+                                   t.al.data(), t.od.data(), (unsigned)t.tcol.size(), t.da.data(), t.db.data(), out); });
+    }
+    // the polynomial's values at rows [first, first + base_lde.num_rows()) of the bit-reversed LDE domain of domain_size points (0: the
+    // matrices hold the whole domain), from those rows of the committed LDE matrices (ms_deep_rows): a whole first FRI layer or a row shard
+    GpuVec<Fp252> into_deep_evaluations(const DeepCompositionCoeffs252& coeffs, const Matrix<Fp252>& base_lde, const Matrix<Fp252>& comp_lde,
+                                        size_t domain_size = 0, size_t first = 0, const f252::E* offset = nullptr) {
+        const size_t count = base_lde.num_rows();
+        if (comp_lde.num_rows() != count) throw std::invalid_argument("into_deep_evaluations: LDE matrices of different heights");
+        if (!domain_size) domain_size = count;
+        unsigned log_N = 0; while (((size_t)1 << log_N) < domain_size) log_N++;
+        return compose(coeffs, base_lde, comp_lde, count, [&](Planner& pl, const std::vector<const void*>& cols, const Terms& t, void* out) {
+            return ms_deep_rows(pl.ctx(), Fp252::id, log_N, offset ? offset->l : nullptr, first, count, cols.data(), (unsigned)cols.size(), nullptr, 0, t.pts.data(), t.npoints,
+                                t.tcol.data(), t.tpoint.data(), t.al.data(), t.od.data(), (unsigned)t.tcol.size(), t.da.data(), t.db.data(), out); });
+    }
+private:
+    struct Terms { std::vector<unsigned> tcol, tpoint; std::vector<uint64_t> pts, al, od, da, db; unsigned npoints = 0; };
+    template <class Call>
+    GpuVec<Fp252> compose(const DeepCompositionCoeffs252& coeffs, const Matrix<Fp252>& b, const Matrix<Fp252>& c, size_t out_len, Call call) {
+        if (!have_ood_) get_ood_evals();
+        std::vector<const void*> cols;
+        for (auto& v : b.columns) cols.push_back(v.ptr());
+        for (auto& v : c.columns) cols.push_back(v.ptr());
+        std::vector<f252::E> points;
+        auto pid = [&](const f252::E& p) { for (size_t k = 0; k < points.size(); k++) if (f252::eq(points[k], p)) return (unsigned)k; points.push_back(p); return (unsigned)points.size() - 1; };
+        Terms t;
+        auto put = [](std::vector<uint64_t>& o, const f252::E& e) { o.insert(o.end(), e.l, e.l + 4); };
+        for (unsigned k = 0; k < comp_.num_cols(); k++) { t.tcol.push_back(nbase_ + k); t.tpoint.push_back(pid(composition_point())); put(t.al, coeffs.composition_trace.at(k)); put(t.od, ood_comp_[k]); }
+        for (size_t k = 0; k < args_.size(); k++) { t.tcol.push_back(args_[k].first); t.tpoint.push_back(pid(point(args_[k].second))); put(t.al, coeffs.execution_trace.at(k)); put(t.od, ood_exec_[k]); }
+        for (auto& p : points) put(t.pts, p);
+        put(t.da, coeffs.degree[0]); put(t.db, coeffs.degree[1]);
+        t.npoints = (unsigned)points.size();
+        Planner& pl = b.planner();
+        GpuVec<Fp252> out(pl, out_len);
+        check(call(pl, cols, t, out.ptr()));
+        return out;
+    }
+    std::vector<std::pair<unsigned, int>> args_;
+    size_t n_; f252::E z_; const Matrix<Fp252>& base_; const Matrix<Fp252>& comp_;
+    f252::E g_, g_inv_; unsigned nbase_ = 0;
+    std::vector<f252::E> ood_exec_, ood_comp_; bool have_ood_ = false;
 };
 
 // ---- RPO-256 front-ends (gpu/src/plan.rs:32-174); digests are 4 Fp elements, Montgomery form

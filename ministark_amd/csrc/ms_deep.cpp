@@ -117,6 +117,81 @@ static int deep_compose252(ms_ctx* ctx, unsigned log_n, const void* h_offset, co
     return MS_OK;
 }
 
+// ms_deep_rows for the 252-bit field: every column is a base column, 4 Montgomery words per element, default offset 3
+static int deep_rows252(ms_ctx* ctx, unsigned log_domain, const void* h_offset, size_t first, size_t count, const void* const* d_rows,
+                        unsigned ncols, const uint64_t* h_points, unsigned npoints, const unsigned* h_term_col, const unsigned* h_term_point,
+                        const uint64_t* h_term_alpha, const uint64_t* h_term_ood, unsigned nterms,
+                        const uint64_t* h_degree_alpha, const uint64_t* h_degree_beta, void* d_out) {
+    if (ncols > (unsigned)msdeep::MAXCOLS) return fail(MS_ERR_UNSUPPORTED, "at most %d columns", msdeep::MAXCOLS);
+    if (npoints == 0 || npoints > (unsigned)msdeep::MAXPOINTS) return fail(MS_ERR_UNSUPPORTED, "1..%d distinct out-of-domain points", msdeep::MAXPOINTS);
+    if (log_domain == 0 || log_domain > 32) return fail(MS_ERR_INVALID, "ms_deep_rows: domain of 2^%u points", log_domain);
+    const size_t N = (size_t)1 << log_domain;
+    if (first > N || count > N - first) return fail(MS_ERR_INVALID, "ms_deep_rows: rows [%zu, %zu) outside the domain", first, first + count);
+    for (unsigned t = 0; t < nterms; t++)
+        if (h_term_col[t] >= ncols || h_term_point[t] >= npoints) return fail(MS_ERR_INVALID, "term %u out of range", t);
+    f252::E h = f252::to_mont(f252::E{{3, 0, 0, 0}});          // the field's generator, as deep_compose252
+    if (h_offset) memcpy(h.l, h_offset, 32);
+    if (f252::is_zero(h) || f252::geq_p(h)) return fail(MS_ERR_INVALID, "coset offset must be a non-zero canonical element");
+    const f252::E hinv = f252::inv(h);
+    for (unsigned k = 0; k < npoints; k++) {                   // a point ON the LDE coset has no quotient there: (z / h)^N = 1
+        f252::E z;
+        memcpy(z.l, h_points + 4 * (size_t)k, 32);
+        if (f252::geq_p(z)) return fail(MS_ERR_INVALID, "ms_deep_rows: out-of-domain point %u is not a canonical element", k);
+        if (f252::is_zero(z)) continue;
+        if (f252::eq(f252::sqr_n(f252::mul(z, hinv), (int)log_domain), f252::one()))
+            return fail(MS_ERR_INVALID, "ms_deep_rows: out-of-domain point %u lies on the LDE coset h<w_N> (x - z vanishes there)", k);
+    }
+    if (count == 0) return MS_OK;
+    // terms sorted by point: a point's quotient factor multiplies the SUM of its terms; csum_k = sum alpha_t ood_t is the sum's constant part
+    std::vector<msdeep252::Term> terms;
+    terms.reserve(nterms);
+    msdeep252::RowsParams D;
+    memset(&D, 0, sizeof D);
+    for (unsigned k = 0; k < npoints; k++) {
+        D.term_start[k] = (unsigned)terms.size();
+        f252::E cs = f252::zero();
+        for (unsigned t = 0; t < nterms; t++) {
+            if (h_term_point[t] != k) continue;
+            msdeep252::Term T;
+            memset(&T, 0, sizeof T);
+            T.col = h_term_col[t]; T.point = k;
+            memcpy(T.alpha, h_term_alpha + 4 * (size_t)t, 32);
+            memcpy(T.ood, h_term_ood + 4 * (size_t)t, 32);
+            f252::E a, o;
+            memcpy(a.l, T.alpha, 32);
+            memcpy(o.l, T.ood, 32);
+            if (f252::geq_p(a) || f252::geq_p(o)) return fail(MS_ERR_INVALID, "ms_deep_rows: term %u holds a non-canonical element", t);
+            cs = f252::add(cs, f252::mul(a, o));
+            terms.push_back(T);
+        }
+        memcpy(D.csum[k], cs.l, 32);
+    }
+    for (unsigned k = npoints; k <= (unsigned)msdeep::MAXPOINTS; k++) D.term_start[k] = (unsigned)terms.size();
+    void* d_terms = nullptr;
+    PoolGuard pooled(ctx);
+    MSCHK(pooled.alloc(std::max<size_t>(1, nterms) * sizeof(msdeep252::Term), &d_terms));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    if (nterms) MSCHK(stage_upload(ctx, d_terms, terms.data(), nterms * sizeof(msdeep252::Term)));
+    ms_ntt_plan* tw = nullptr;
+    MSCHK(plan252_cached(ctx, log_domain, false, f252::one(), &tw));           // its tables hold w_N^i
+    for (unsigned c = 0; c < ncols; c++) D.cols[c] = (const uint64_t*)d_rows[c];
+    D.terms = (const msdeep252::Term*)d_terms; D.tw_lo = tw->d252_tw_lo; D.tw_hi = tw->d252_tw_hi; D.lo_bits = tw->lo_bits;
+    memcpy(D.points, h_points, (size_t)npoints * 32);
+    memcpy(D.h, h.l, 32);
+    memcpy(D.adj_alpha, h_degree_alpha, 32);
+    memcpy(D.adj_beta, h_degree_beta, 32);
+    D.out = (uint64_t*)d_out; D.n = count; D.first = first; D.npoints = npoints; D.log_dom = log_domain;
+    {
+        ProfScope ps(ctx, "deep_rows252", 32.0 * count * (ncols + 1));
+        constexpr int R = msdeep252::ROWS_PER_LANE, W = msdeep252::ROWS_WAVES;
+        const size_t per = (size_t)64 * W * R;
+        hipLaunchKernelGGL((msdeep252::deep_rows<R, W>), dim3((unsigned)((count + per - 1) / per)), dim3(64 * W), 0, ctx->stream, D);
+    }
+    HIPCHK(hipGetLastError());
+    return MS_OK;
+}
+
 extern "C" int ms_horner_eval(ms_ctx* ctx, int coeff_field, int point_field, size_t n, const void* const* d_cols, unsigned ncols,
                               const unsigned* h_qcol, const void* h_qpoints, unsigned nq, void* h_out) {
     if (!ctx || !d_cols || !h_qcol || !h_qpoints || !h_out) return fail(MS_ERR_INVALID, "ms_horner_eval: null argument");
@@ -363,7 +438,13 @@ extern "C" int ms_deep_rows(ms_ctx* ctx, int point_field, unsigned log_domain, c
                             const void* h_degree_alpha, const void* h_degree_beta, void* d_out) {
     if (!ctx || !h_points || !h_term_col || !h_term_point || !h_term_alpha || !h_term_ood || !h_degree_alpha || !h_degree_beta || !d_out)
         return fail(MS_ERR_INVALID, "ms_deep_rows: null argument");
-    if (point_field == MS_STARK252_FP) return fail(MS_ERR_UNSUPPORTED, "ms_deep_rows: Goldilocks fields only (the 252-bit composer goes through ms_deep_compose)");
+    if (point_field == MS_STARK252_FP) {
+        if (next) return fail(MS_ERR_INVALID, "the 252-bit field has no extension columns: pass every column as a base column");
+        if (nbase && !d_base_rows) return fail(MS_ERR_INVALID, "ms_deep_rows: null column table");
+        return deep_rows252(ctx, log_domain, h_offset, first, count, d_base_rows, nbase, (const uint64_t*)h_points, npoints, h_term_col, h_term_point,
+                            (const uint64_t*)h_term_alpha, (const uint64_t*)h_term_ood, nterms, (const uint64_t*)h_degree_alpha,
+                            (const uint64_t*)h_degree_beta, d_out);
+    }
     unsigned PW = 0;
     MSCHK(point_words(point_field, &PW));
     if (PW == 1 && next) return fail(MS_ERR_INVALID, "extension columns need point_field = Fq3");

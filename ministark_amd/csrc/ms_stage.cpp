@@ -215,7 +215,6 @@ static int fri_fold_impl(ms_ctx* ctx, int field, unsigned log_n, unsigned foldin
     if (log_n < log_ff || log_n > 32) return fail(MS_ERR_INVALID, "bad layer size 2^%u for folding factor %u", log_n, folding_factor);
     const size_t all_chunks = (size_t)1 << (log_n - log_ff);
     if (whole) { first_chunk = 0; nchunks = all_chunks; }
-    else if (V == 4) return fail(MS_ERR_UNSUPPORTED, "ms_fri_fold_rows: Goldilocks fields");
     if (first_chunk > all_chunks || nchunks > all_chunks - first_chunk) return fail(MS_ERR_INVALID, "ms_fri_fold_rows: chunks [%zu, %zu) outside the layer", first_chunk, first_chunk + nchunks);
     if (nchunks == 0) return MS_OK;
     {   // lane c reads d_evals[c*ff .. c*ff + ff) and writes d_out[c]: overlapping buffers would corrupt the next layer
@@ -241,9 +240,10 @@ static int fri_fold_impl(ms_ctx* ctx, int field, unsigned log_n, unsigned foldin
         const f252::E zinv = f252::pow_u64(f252::inv(f252::root_of_unity(log_n)), (uint64_t)1 << (log_n - log_ff));
         f252::E zp = f252::one();
         for (unsigned k = 0; k < folding_factor / 2; k++) { memcpy(P.zinv[k], zp.l, 32); zp = f252::mul(zp, zinv); }
-        const size_t m = (size_t)1 << (log_n - log_ff);
+        P.first_chunk = first_chunk; P.nchunks = nchunks;
+        const size_t m = nchunks;
         dim3 g((unsigned)((m + ms252::NT - 1) / ms252::NT));
-        ProfScope ps(ctx, "fri_fold252", 32.0 * (((size_t)1 << log_n) + m));
+        ProfScope ps(ctx, "fri_fold252", 32.0 * (m * folding_factor + m));
         switch (folding_factor) {
         case 2: hipLaunchKernelGGL(ms252::fri_fold252<2>, g, dim3(ms252::NT), 0, ctx->stream, P); break;
         case 4: hipLaunchKernelGGL(ms252::fri_fold252<4>, g, dim3(ms252::NT), 0, ctx->stream, P); break;

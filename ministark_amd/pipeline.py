@@ -26,8 +26,8 @@ import time
 import numpy as np
 
 from . import expr as E
-from .api import (GL_P, GOLDILOCKS_FP, Matrix, MerkleTree, Queries, Radix2EvaluationDomain, apply_drp, gl_to_mont,
-                  grind_proof_of_work, pow_hash)
+from .api import (F252_P, GL_P, GOLDILOCKS_FP, STARK252_FP, Matrix, MerkleTree, Queries, Radix2EvaluationDomain, apply_drp, f252_to_mont_limbs,
+                  gl_to_mont, grind_proof_of_work, pow_hash)
 from .composer import DeepCompositionCoeffs, DeepPolyComposer
 
 
@@ -144,12 +144,32 @@ def mixed_air_constraints():
     return expr, 4
 
 
-class Draws:
-    """What the verifier's coin would supply, fixed up front (canonical integers of Fp)."""
+def field_modulus(field):
+    return F252_P if field == STARK252_FP else GL_P
 
-    def __init__(self, seed, ncols, nchallenges, ce_blowup, nqueries, n_lde, nlayers):
+
+def field_generator(field):
+    """the coset offset of the LDE domain: the field's multiplicative generator (7 for Goldilocks, 3 for the 252-bit field)"""
+    return 3 if field == STARK252_FP else 7
+
+
+def to_mont_words(field, values):
+    """canonical integers of the base field -> their Montgomery words, one row per element (1 word, or 4 for the 252-bit field)"""
+    if field == STARK252_FP:
+        return np.array([f252_to_mont_limbs(int(v) % F252_P) for v in values], dtype=np.uint64).reshape(-1, 4)
+    return np.array([gl_to_mont(v) for v in values], dtype=np.uint64).reshape(-1, 1)
+
+
+class Draws:
+    """What the verifier's coin would supply, fixed up front (canonical integers of Fp).  modulus: the field the draws are made
+    under (the Goldilocks prime by default; its draws are what they always were)."""
+
+    def __init__(self, seed, ncols, nchallenges, ce_blowup, nqueries, n_lde, nlayers, modulus=GL_P):
         rng = np.random.default_rng(seed)
-        r = lambda k: [int(v) for v in rng.integers(1, GL_P, size=k, dtype=np.uint64)]
+        if modulus == GL_P:
+            r = lambda k: [int(v) for v in rng.integers(1, GL_P, size=k, dtype=np.uint64)]
+        else:
+            r = lambda k: [1 + int.from_bytes(rng.bytes(40), "little") % (modulus - 1) for _ in range(k)]
         self.challenges = r(nchallenges)                                        # the composition coefficients (alpha_i, beta_i)
         self.hints = r(1)                                                       # FibHint::ClaimedNthFibNum
         self.z = r(1)[0]
@@ -208,36 +228,43 @@ def fri_num_layers(n_lde, blowup, folding, max_remainder_coeffs):
 _LOWERED = {}
 
 
-def _lowered(comp_expr, ncols):
+def _lowered(comp_expr, ncols, field=GOLDILOCKS_FP):
     """The register program of an AIR's composition constraint, lowered once per expression object (an AIR's constraints are fixed; the
     C++ example compiles its program outside the proof loop as well).  Keyed by identity: the expression is kept alive by the entry."""
-    key = (id(comp_expr), ncols)
+    key = (id(comp_expr), ncols, field)
     hit = _LOWERED.get(key)
     if hit is None or hit[0] is not comp_expr:
         if len(_LOWERED) > 16:
             _LOWERED.clear()
-        hit = (comp_expr, E.compile_expr(comp_expr, ncols, False))
+        hit = (comp_expr, E.compile_expr(comp_expr, ncols, False, field))
         _LOWERED[key] = hit
     return hit[1]
 
 
 def prove_phases(planner, trace, comp_expr, draws, blowup=4, folding=8, max_remainder_coeffs=64, grinding_bits=8, hash="sha256",
-                 keep=False, ce_blowup=None, time_phases=True):
-    """trace: Matrix of Fp columns (2^k rows).  ce_blowup: the AIR's ce_blowup_factor (src/air.rs:55-59; the constraint
+                 keep=False, ce_blowup=None, time_phases=True, field=GOLDILOCKS_FP):
+    """trace: Matrix of Fp columns (2^k rows).  field: GOLDILOCKS_FP, or STARK252_FP (trace, draws and constraints over the 252-bit
+    field, LDE offset 3; commits with "sha256" or "blake2s" -- RPO-256 absorbs Goldilocks elements).  ce_blowup: the AIR's ce_blowup_factor (src/air.rs:55-59; the constraint
     evaluation domain has trace_len * ce_blowup points, the composition trace ce_blowup columns); None = the LDE blow-up.
     Returns dict(roots=..., fri_roots=[...], remainder=GpuVec, nonce=int, queries=Queries, phases_ms={...}); with keep=True
     also the intermediate device objects (for parity tests).  time_phases=False: no device wait at the phase boundaries (two of the six
     are waits the proof itself does not need: after the evaluation and after DEEP) and no `phases_ms`."""
     pl = planner
+    if field not in (GOLDILOCKS_FP, STARK252_FP):
+        raise ValueError("prove_phases: field must be GOLDILOCKS_FP or STARK252_FP")
+    if field == STARK252_FP and hash == "rpo256":
+        raise ValueError("prove_phases: RPO-256 absorbs Goldilocks elements; the 252-bit field commits with sha256 or blake2s")
+    if field == STARK252_FP and trace.field != field:
+        raise ValueError("prove_phases: field=STARK252_FP needs a trace over that field")
+    h = field_generator(field)
     n_t = trace.num_rows()
     n_lde = n_t * blowup
     ce_blowup = blowup if ce_blowup is None else ce_blowup
     assert ce_blowup <= blowup                                                 # src/air.rs:149
     n_ce = n_t * ce_blowup
-    trace_dom, lde_dom, ce_dom = Radix2EvaluationDomain(n_t), Radix2EvaluationDomain(n_lde, 7), Radix2EvaluationDomain(n_ce, 7)
-    prog = _lowered(comp_expr, trace.num_cols())
-    ch = np.array([gl_to_mont(c) for c in draws.challenges], dtype=np.uint64).reshape(-1, 1)
-    hints = np.array([gl_to_mont(c) for c in draws.hints], dtype=np.uint64).reshape(-1, 1)
+    trace_dom, lde_dom, ce_dom = Radix2EvaluationDomain(n_t, 1, field), Radix2EvaluationDomain(n_lde, h, field), Radix2EvaluationDomain(n_ce, h, field)
+    prog = _lowered(comp_expr, trace.num_cols(), field)
+    ch, hints = to_mont_words(field, draws.challenges), to_mont_words(field, draws.hints)
     out, phase = {}, {}
     t = time.perf_counter()
 
@@ -257,7 +284,7 @@ def prove_phases(planner, trace, comp_expr, draws, blowup=4, folding=8, max_rema
     lap("base trace: interpolate + LDE + commit")
     # the first n_ce rows of the committed (bit-reversed) LDE are the constraint-evaluation coset in its own bit-reversed order:
     # the evaluator works on them where they lie (the reference re-orders them, bit_reverse_ce_trace, prover.rs:88-91)
-    comp_evals = E.eval(prog, pl, ch, hints, ce_blowup, 7, n_ce, lde_t.columns, bit_reversed=True)      # prover.rs:97-107
+    comp_evals = E.eval(prog, pl, ch, hints, ce_blowup, h, n_ce, lde_t.columns, bit_reversed=True)      # prover.rs:97-107
     lap("constraint evaluation")
     kept_evals = comp_evals.clone() if keep else None                          # the next two steps work in place
     comp_poly = Matrix([comp_evals]).bit_reverse_rows().into_polynomials(ce_dom).columns[0]             # prover.rs:111-112
@@ -282,12 +309,12 @@ def prove_phases(planner, trace, comp_expr, draws, blowup=4, folding=8, max_rema
         fri_layers.append(cur); fri_trees.append(tree)                        # FriLayer { merkle_tree, evaluations } (fri.rs:218-221)
         if keep:
             layers.append(cur)
-        cur = apply_drp(cur, np.array([gl_to_mont(alpha)], dtype=np.uint64), folding, 1)
+        cur = apply_drp(cur, to_mont_words(field, [alpha]).ravel(), folding, 1)
         n //= folding
     out["fri_roots"], out["remainder"] = roots, cur
     # FriProver::set_remainder (fri.rs:232-248): bit_reverse, iNTT over the subgroup of the remainder's size, keep n / blowup coefficients
-    rem = Matrix([cur.clone()]).bit_reverse_rows().into_polynomials(Radix2EvaluationDomain(n)).columns[0]
-    out["remainder_coeffs"] = rem.to_numpy()[: max(n // blowup, 1)]
+    rem = Matrix([cur.clone()]).bit_reverse_rows().into_polynomials(Radix2EvaluationDomain(n, 1, field)).columns[0]
+    out["remainder_coeffs"] = rem.to_numpy()[: max(n // blowup, 1) * (4 if field == STARK252_FP else 1)]
     lap("FRI layers (commit + fold) + remainder")
     fine, tf = {}, time.perf_counter()
 
