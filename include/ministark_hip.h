@@ -140,9 +140,18 @@ int ms_deinterleave(ms_ctx* ctx, int field, size_t n_out, unsigned k, const void
 /* ---- element-wise stages (gpu/src/stage.rs:115-1155; kernels evaluation_shaders.h.metal:11-168).
  * lf / rf are the fields of lhs(=dst) and rhs: (Fp,Fp), (Fq3,Fq3) or (Fq3,Fp) -- the GpuMul / GpuAdd
  * impls of gpu/src/fields.rs:55-216.  `shift` rotates the rhs index: rhs[(i + shift) mod n], any sign
- * (the reference normalises with (n + shift) % n, stage.rs:168,227,449,515).  d_dst may alias d_lhs
- * (the *Assign / *InPlace stages) but not d_rhs when shift != 0.  All calls are asynchronous.
- *   ms_binary        MulAssign / MulInto / AddAssign / AddInto            (stage.rs:115-233, 393-521)
+ * (the reference normalises with (n + shift) % n, stage.rs:168,227,449,515).  `n` is any length (the power-of-two rule of
+ * stage.rs:55-59 is the wrappers'); n == 0 is MS_OK and touches nothing.  All calls are asynchronous.
+ * Aliasing: every lane reads and writes its own index only, so a destination is either the SAME buffer as a source (the
+ * *Assign / *InPlace stages) or disjoint from it.  Anything else is refused with MS_ERR_INVALID ("... overlap ...") before
+ * anything is enqueued; the buffers are left as they were.  Ranges are compared by bytes: n elements of the buffer's field.
+ *   ms_binary, ms_mul_pow      d_dst == d_lhs or disjoint.  d_dst and d_rhs disjoint; d_dst == d_rhs only with lf == rf and
+ *                              shift == 0 (mod n) (squaring / doubling in place) -- never an Fq3 dst at an Fp rhs
+ *   ms_binary_const, ms_unary  d_dst == the source or disjoint
+ *   ms_convert                 equal fields: d_dst == d_src is a no-op, disjoint buffers are copied, a partial overlap is
+ *                              refused; Fp -> Fq3: any overlap is refused (there is no in-place embedding)
+ *   ms_sum_columns             d_dst == a column or disjoint from it, for every column; columns may alias each other
+ *   ms_binary       MulAssign / MulInto / AddAssign / AddInto            (stage.rs:115-233, 393-521)
  *   ms_binary_const  {Mul,Add}{Into,Assign}Const                          (stage.rs:523-806)
  *   ms_mul_pow       MulPowStage: dst = lhs * rhs[(i+shift)%n]^power      (stage.rs:334-391)
  *   ms_unary         Neg / Inverse / Exp, in place or into                (stage.rs:808-1109);

@@ -23,15 +23,34 @@ static size_t norm_shift(long shift, size_t n) {
     if (m < 0) m += (long long)n;
     return (size_t)m;
 }
+// Byte ranges [a, a + na) and [b, b + nb) of device memory, as fri_fold_impl compares them.  A stage lane reads and writes its own
+// index only, so a destination that IS a source (same address) is the in-place form; any other overlap has lanes reading words that
+// other lanes write -- a data race on the device.  Checked before anything is enqueued.
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const char *p = (const char*)a, *q = (const char*)b;
+    return p < q + nb && q < p + na;
+}
+static int disjoint_or_same(const char* entry, const char* what, const void* d_dst, size_t dst_bytes, const void* d_src, size_t src_bytes, bool same_ok = true) {
+    if (d_dst == d_src && same_ok) return MS_OK;
+    if (ranges_overlap(d_dst, dst_bytes, d_src, src_bytes))
+        return fail(MS_ERR_INVALID, "%s: d_dst and %s overlap (%s)", entry, what, same_ok ? "they must be disjoint or the same buffer" : "they must be disjoint here");
+    return MS_OK;
+}
+// dst against lhs and the rotated rhs: dst == rhs is a lane reading its own index only for equal fields and a shift of 0 (mod n)
+static int binary_overlap(const char* entry, size_t n, unsigned VL, unsigned VR, size_t sh, const void* d_dst, const void* d_lhs, const void* d_rhs) {
+    MSCHK(disjoint_or_same(entry, "d_lhs", d_dst, n * VL * 8, d_lhs, n * VL * 8));
+    return disjoint_or_same(entry, "d_rhs", d_dst, n * VL * 8, d_rhs, n * VR * 8, VL == VR && sh == 0);
+}
 extern "C" int ms_binary(ms_ctx* ctx, int op, int lf, int rf, size_t n, void* d_dst, const void* d_lhs, const void* d_rhs, long shift) {
     if (!ctx || !d_dst || !d_lhs || !d_rhs) return fail(MS_ERR_INVALID, "ms_binary: null argument");
     if (op != MS_ADD && op != MS_MUL) return fail(MS_ERR_INVALID, "unknown binary op %d", op);
     unsigned VL = 0, VR = 0;
     MSCHK(field_pair(lf, rf, &VL, &VR));
     if (n == 0) return MS_OK;
+    const size_t sh = norm_shift(shift, n);
+    MSCHK(binary_overlap("ms_binary", n, VL, VR, sh, d_dst, d_lhs, d_rhs));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t sh = norm_shift(shift, n);
     uint64_t* dst = (uint64_t*)d_dst; const uint64_t* l = (const uint64_t*)d_lhs; const uint64_t* r = (const uint64_t*)d_rhs;
     dim3 g(stream_grid(n)), b(msstage::NT);
     ProfScope ps(ctx, op == MS_ADD ? "stage_add" : "stage_mul", 8.0 * n * (2 * VL + VR));
@@ -53,6 +72,7 @@ extern "C" int ms_binary_const(ms_ctx* ctx, int op, int lf, int rf, size_t n, vo
     unsigned VL = 0, VR = 0;
     MSCHK(field_pair(lf, rf, &VL, &VR));
     if (n == 0) return MS_OK;
+    MSCHK(disjoint_or_same("ms_binary_const", "d_lhs", d_dst, n * VL * 8, d_lhs, n * VL * 8));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     msstage::Const3 c = {{0, 0, 0, 0}};
@@ -77,9 +97,10 @@ extern "C" int ms_mul_pow(ms_ctx* ctx, int lf, int rf, size_t n, void* d_dst, co
     unsigned VL = 0, VR = 0;
     MSCHK(field_pair(lf, rf, &VL, &VR));
     if (n == 0) return MS_OK;
+    const size_t sh = norm_shift(shift, n);
+    MSCHK(binary_overlap("ms_mul_pow", n, VL, VR, sh, d_dst, d_lhs, d_rhs));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t sh = norm_shift(shift, n);
     uint64_t* dst = (uint64_t*)d_dst; const uint64_t* l = (const uint64_t*)d_lhs; const uint64_t* r = (const uint64_t*)d_rhs;
     dim3 g(stream_grid(n)), b(msstage::NT);
     ProfScope ps(ctx, "stage_mul_pow", 8.0 * n * (2 * VL + VR));
@@ -97,6 +118,7 @@ extern "C" int ms_unary(ms_ctx* ctx, int op, int field, size_t n, void* d_dst, c
     unsigned V = 0;
     MSCHK(field_words(field, &V));
     if (n == 0) return MS_OK;
+    MSCHK(disjoint_or_same("ms_unary", "d_src", d_dst, n * V * 8, d_src, n * V * 8));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     uint64_t* dst = (uint64_t*)d_dst; const uint64_t* src = (const uint64_t*)d_src;
@@ -132,6 +154,8 @@ extern "C" int ms_convert(ms_ctx* ctx, int dst_field, int src_field, size_t n, v
     unsigned VD = 0, VS = 0;
     MSCHK(field_pair(dst_field, src_field, &VD, &VS));
     if (n == 0) return MS_OK;
+    // equal fields: the same buffer is a no-op, disjoint ones a copy; the embedding writes 3 words per word read and has no in-place form
+    MSCHK(disjoint_or_same("ms_convert", "d_src", d_dst, n * VD * 8, d_src, n * VS * 8, VD == VS));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     if (VD == VS) {
@@ -165,6 +189,10 @@ extern "C" int ms_sum_columns(ms_ctx* ctx, int field, size_t n, const void* cons
     if (ncols == 0) return fail(MS_ERR_INVALID, "sum of zero columns");
     if (ncols > (unsigned)msstage::MAXCOLS) return fail(MS_ERR_UNSUPPORTED, "at most %d columns per call", msstage::MAXCOLS);
     if (n == 0) return MS_OK;
+    for (unsigned c = 0; c < ncols; c++) {        // columns are only read and may alias each other; lane i reads cols[c][i] before it writes dst[i]
+        if (!d_cols[c]) return fail(MS_ERR_INVALID, "ms_sum_columns: null column %u", c);
+        MSCHK(disjoint_or_same("ms_sum_columns", "a column", d_dst, n * V * 8, d_cols[c], n * V * 8));
+    }
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     msstage::SumParams P;

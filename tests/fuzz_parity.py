@@ -2,7 +2,7 @@
 """Randomised differential run of the library against the C oracle (oracle/c) on the GPU:
     python tests/fuzz_parity.py [seconds] [seed]
 Random sizes (2^0 .. 2^21: every plan family incl. the (256, R, 256) ones), fields, directions, coset offsets, blow-ups, folding factors, shifts and column
-counts; values are a mix of uniform elements and edge values (0, 1, p-1, 2^32-1, 2^32, p-2^32 ...).
+counts; the element-wise stages run through the C ABI at any length up to 2^15, not only powers of two; values are a mix of uniform elements and edge values (0, 1, p-1, 2^32-1, 2^32, p-2^32 ...).
 Complements tests/ (fixed shapes): any mismatch prints the failing case and exits non-zero.  MS_FUZZ_BACKEND=emu: the same on the simulator build
 (CPU; transforms to 2^18, LDEs to 2^14 rows)."""
 import sys
@@ -97,21 +97,44 @@ def case_commit():
 
 
 def case_stage():
-    log_n = int(rng.integers(0, 15))
-    n = 1 << log_n
+    # through the C ABI, where n is free (the stage wrappers keep the reference's power-of-two rule): any length up to 2^15
+    n = int(rng.integers(1, (1 << 15) + 1)) if rng.integers(0, 4) else 1 << int(rng.integers(0, 16))
     lf, rf = [(FP, FP), (FQ3, FQ3), (FQ3, FP)][int(rng.integers(0, 3))]
     VL, VR = (3 if lf == FQ3 else 1), (3 if rf == FQ3 else 1)
     a, b, shift, e = values(n * VL), values(n * VR), int(rng.integers(-2 * n, 2 * n + 1)), int(rng.integers(0, 40))
     A, B, D = GpuVec.from_numpy(pl, a, lf), GpuVec.from_numpy(pl, b, rf), GpuVec(pl, n, lf)
-    S.MulIntoStage(pl, n, lf, rf).encode(D, A, B, shift)
+    L, h = pl.lib, pl.handle
+    L.check(L.ms_binary(h, S.MUL, lf, rf, n, D.ptr, A.ptr, B.ptr, shift))
     ok = np.array_equal(D.to_numpy(), cref.binary(1, VL, VR, a, b, shift))
-    S.AddIntoStage(pl, n, lf, rf).encode(D, A, B, shift)
+    L.check(L.ms_binary(h, S.ADD, lf, rf, n, D.ptr, A.ptr, B.ptr, shift))
     ok &= np.array_equal(D.to_numpy(), cref.binary(0, VL, VR, a, b, shift))
-    S.MulPowStage(pl, n, lf, rf).encode(A, B, e, shift)
+    # the const stages, into another buffer and in place
+    c, op = values(VR), int(rng.integers(0, 2))
+    L.check(L.ms_binary_const(h, op, lf, rf, n, D.ptr, A.ptr, c.ctypes.data))
+    ok &= np.array_equal(D.to_numpy(), cref.binary_const(op, VL, VR, a, c))
+    L.check(L.ms_binary_const(h, 1 - op, lf, rf, n, D.ptr, D.ptr, c.ctypes.data))
+    ok &= np.array_equal(D.to_numpy(), cref.binary_const(1 - op, VL, VR, cref.binary_const(op, VL, VR, a, c), c))
+    L.check(L.ms_mul_pow(h, lf, rf, n, A.ptr, A.ptr, B.ptr, e, shift))
     ok &= np.array_equal(A.to_numpy(), cref.mul_pow(VL, VR, a, b, e, shift))
-    S.InverseIntoStage(pl, n, lf).encode(D, A)
+    L.check(L.ms_unary(h, S.INV, lf, n, D.ptr, A.ptr, 0))
     ok &= np.array_equal(D.to_numpy(), cref.unary(1, VL, A.to_numpy(), 0))
-    return bool(ok), f"stage log_n={log_n} fields=({VL},{VR}) shift={shift} e={e}"
+    # ConvertInto (the embedding, or the copy between equal fields), FillBuff, sum_columns (dst is sometimes one of the columns)
+    L.check(L.ms_convert(h, lf, rf, n, D.ptr, B.ptr))
+    emb = np.zeros((n, VL), dtype=np.uint64)
+    emb[:, :VR] = b.reshape(n, VR)
+    ok &= np.array_equal(D.to_numpy(), emb.reshape(-1))
+    fill = values(VL)
+    L.check(L.ms_fill(h, lf, n, D.ptr, fill.ctypes.data))
+    ok &= np.array_equal(D.to_numpy(), np.tile(fill, n))
+    ncols = int(rng.choice([1, 2, 3, 17, 127, 128]))
+    cols = [values(n * VL) for _ in range(min(ncols, 4))]
+    vecs = [GpuVec.from_numpy(pl, x, lf) for x in cols]
+    idx = [int(k) for k in rng.integers(0, len(cols), size=ncols)]              # columns may alias each other
+    dst = vecs[idx[int(rng.integers(0, ncols))]] if rng.integers(0, 2) else D
+    arr = (__import__("ctypes").c_void_p * ncols)(*[vecs[k].ptr for k in idx])
+    L.check(L.ms_sum_columns(h, lf, n, arr, ncols, dst.ptr))
+    ok &= np.array_equal(dst.to_numpy(), cref.sum_columns([cols[k] for k in idx], VL))
+    return bool(ok), f"stage n={n} fields=({VL},{VR}) shift={shift} e={e} const_op={op} ncols={ncols}"
 
 
 CASES = [case_ntt, case_lde, case_evaluate, case_fri, case_commit, case_stage]
