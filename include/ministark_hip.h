@@ -359,7 +359,17 @@ int ms_fri_fold_rows(ms_ctx* ctx, int field, unsigned log_n, unsigned folding_fa
  *                  MS_STARK252_FP: every column is a base column (next must be 0, MS_ERR_INVALID otherwise), points / alphas /
  *                  values are 4 Montgomery words each, h_offset NULL = the field's generator 3.  A point that lies on the LDE
  *                  coset, a zero or non-canonical offset, rows outside the domain: MS_ERR_INVALID, nothing written.  The words
- *                  do not depend on how the domain is split into calls.  Asynchronous. */
+ *                  do not depend on how the domain is split into calls.  Asynchronous.
+ * Rules of ms_deep_compose and ms_deep_rows (tests/test_deep_sweep.py):
+ *   - 1..8 points, at most 96 columns of each kind (MS_ERR_UNSUPPORTED otherwise); a point that no term names contributes nothing.
+ *   - nterms = 0: the output is all zero (the term arrays must still be non-null).
+ *   - ms_deep_compose accepts log_n = 0 and 1 and returns what the reference's synthetic division returns (n = 1: the single
+ *     coefficient 0; n = 2: the constant quotient and its degree adjustment).  ms_deep_rows needs log_domain >= 1.
+ *   - a point on the evaluation coset h<w_n> (ms_deep_compose, every field) or on the LDE coset (ms_deep_rows): MS_ERR_INVALID.
+ *   - d_out must not overlap any input column, not even as the same buffer: there is no in-place form (a lane of ms_deep_rows past
+ *     the end of a ragged shard reads row 0 of every column while other lanes store).  MS_ERR_INVALID with "overlap" in
+ *     ms_last_error(), before anything is enqueued; buffers that merely touch are fine.
+ *   Every refusal above returns before anything is enqueued and writes nothing. */
 int ms_horner_eval(ms_ctx* ctx, int coeff_field, int point_field, size_t n, const void* const* d_cols, unsigned ncols,
                    const unsigned* h_qcol, const void* h_qpoints, unsigned nq, void* h_out);
 int ms_deep_rows(ms_ctx* ctx, int point_field, unsigned log_domain, const void* h_offset, size_t first, size_t count,

@@ -12,6 +12,16 @@ static int point_words(int point_field, unsigned* PW) {
     if (point_field == MS_GOLDILOCKS_FQ3) { *PW = 3; return MS_OK; }
     return fail(MS_ERR_UNSUPPORTED, "point field must be Goldilocks Fp or Fq3");
 }
+// d_out against every input column: ms_deep_rows' lanes past the end of a ragged shard read row 0 of every column while other lanes store, and
+// an Fq3 output row is three words of an Fp column's: there is no in-place form.  ms_deep_compose has transformed every column into scratch
+// before it writes d_out, but it keeps the same rule (one rule for both entry points, and the order of its passes stays free): any overlap,
+// the same address included, is refused before anything is enqueued.
+static int out_overlaps_no_column(const char* entry, const void* d_out, size_t out_bytes, const void* const* cols, unsigned ncols, size_t col_bytes, const char* kind) {
+    for (unsigned c = 0; c < ncols; c++)
+        if (ranges_overlap(d_out, out_bytes, cols[c], col_bytes))
+            return fail(MS_ERR_INVALID, "%s: d_out and %s column %u overlap (the output must be disjoint from every input column)", entry, kind, c);
+    return MS_OK;
+}
 static gl::Fq3 q3_load(const uint64_t* p, unsigned PW) { return PW == 3 ? gl::Fq3{p[0], p[1], p[2]} : gl::Fq3{p[0], 0, 0}; }
 
 // ---- the 252-bit instantiations (Fq = Fp = Fp252)
@@ -71,6 +81,18 @@ static int deep_compose252(ms_ctx* ctx, unsigned log_n, const void* h_offset, co
     if (h_offset) memcpy(h.l, h_offset, 32);
     if (f252::is_zero(h) || f252::geq_p(h)) return fail(MS_ERR_INVALID, "coset offset must be a non-zero canonical element");
     const size_t n = (size_t)1 << log_n;
+    {   // a point ON the evaluation coset has no quotient there: (z / h)^n = 1 (as ms_deep_compose over Goldilocks and deep_rows252 refuse it)
+        const f252::E hinv = f252::inv(h);
+        for (unsigned k = 0; k < npoints; k++) {
+            f252::E z;
+            memcpy(z.l, h_points + 4 * (size_t)k, 32);
+            if (f252::geq_p(z)) return fail(MS_ERR_INVALID, "ms_deep_compose: out-of-domain point %u is not a canonical element", k);
+            if (f252::is_zero(z)) continue;
+            if (f252::eq(f252::sqr_n(f252::mul(z, hinv), (int)log_n), f252::one()))
+                return fail(MS_ERR_INVALID, "ms_deep_compose: out-of-domain point %u lies on the evaluation coset h<w_n> (x - z vanishes there)", k);
+        }
+    }
+    MSCHK(out_overlaps_no_column("ms_deep_compose", d_out, n * 32, d_polys, ncols, n * 32, "base"));
     std::vector<void*> ev(ncols, nullptr);
     void *d_terms = nullptr, *d_q = nullptr;
     PoolGuard pooled(ctx);                                 // temporaries go back to the pool on every exit path
@@ -141,6 +163,7 @@ static int deep_rows252(ms_ctx* ctx, unsigned log_domain, const void* h_offset, 
         if (f252::eq(f252::sqr_n(f252::mul(z, hinv), (int)log_domain), f252::one()))
             return fail(MS_ERR_INVALID, "ms_deep_rows: out-of-domain point %u lies on the LDE coset h<w_N> (x - z vanishes there)", k);
     }
+    MSCHK(out_overlaps_no_column("ms_deep_rows", d_out, count * 32, d_rows, ncols, count * 32, "base"));
     if (count == 0) return MS_OK;
     // terms sorted by point: a point's quotient factor multiplies the SUM of its terms; csum_k = sum alpha_t ood_t is the sum's constant part
     std::vector<msdeep252::Term> terms;
@@ -340,6 +363,8 @@ extern "C" int ms_deep_compose(ms_ctx* ctx, int point_field, unsigned log_n, con
         if (z != 0 && gl::pow(gl::mul(z, gl::inv(h)), n) == 1)
             return fail(MS_ERR_INVALID, "ms_deep_compose: out-of-domain point %u lies on the evaluation coset h<w_n> (x - z vanishes there)", k);
     }
+    MSCHK(out_overlaps_no_column("ms_deep_compose", d_out, n * PW * 8, d_base_polys, nbase, n * 8, "base"));
+    MSCHK(out_overlaps_no_column("ms_deep_compose", d_out, n * PW * 8, d_ext_polys, next, n * 24, "extension"));
     // scratch: coset evaluations of every polynomial + the evaluation/coefficient column of Q
     std::vector<void*> ev(nbase + next, nullptr);
     void *d_terms = nullptr, *d_q = nullptr;
@@ -466,6 +491,8 @@ extern "C" int ms_deep_rows(ms_ctx* ctx, int point_field, unsigned log_domain, c
         if (z != 0 && gl::pow(gl::mul(z, gl::inv(h)), N) == 1)
             return fail(MS_ERR_INVALID, "ms_deep_rows: out-of-domain point %u lies on the LDE coset h<w_N> (x - z vanishes there)", k);
     }
+    MSCHK(out_overlaps_no_column("ms_deep_rows", d_out, count * PW * 8, d_base_rows, nbase, count * 8, "base"));
+    MSCHK(out_overlaps_no_column("ms_deep_rows", d_out, count * PW * 8, d_ext_rows, next, count * 24, "extension"));
     if (count == 0) return MS_OK;
     std::vector<msdeep::Term> terms;
     terms.reserve(nterms);

@@ -33,6 +33,12 @@ int field_words(int field, unsigned* V);
         int r_ = (expr);           \
         if (r_ != MS_OK) return r_; \
     } while (0)
+// Byte ranges [a, a + na) and [b, b + nb) of device memory, as fri_fold_impl compares them (an empty range overlaps nothing).  The entry points
+// that refuse overlapping buffers (ms_stage.cpp, ms_deep.cpp) check with this before anything is enqueued.
+static inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const char *p = (const char*)a, *q = (const char*)b;
+    return p < q + nb && q < p + na;
+}
 
 
 // what the specialised constraint kernels cost and where they came from (eval_jit.h, jit_cache.h; ms_eval_jit_stats)

@@ -23,13 +23,9 @@ static size_t norm_shift(long shift, size_t n) {
     if (m < 0) m += (long long)n;
     return (size_t)m;
 }
-// Byte ranges [a, a + na) and [b, b + nb) of device memory, as fri_fold_impl compares them.  A stage lane reads and writes its own
+// ranges_overlap (ms_internal.h) on the stages' buffers.  A stage lane reads and writes its own
 // index only, so a destination that IS a source (same address) is the in-place form; any other overlap has lanes reading words that
 // other lanes write -- a data race on the device.  Checked before anything is enqueued.
-static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const char *p = (const char*)a, *q = (const char*)b;
-    return p < q + nb && q < p + na;
-}
 static int disjoint_or_same(const char* entry, const char* what, const void* d_dst, size_t dst_bytes, const void* d_src, size_t src_bytes, bool same_ok = true) {
     if (d_dst == d_src && same_ok) return MS_OK;
     if (ranges_overlap(d_dst, dst_bytes, d_src, src_bytes))

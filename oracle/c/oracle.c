@@ -786,7 +786,10 @@ void oracle_horner_eval(const uint64_t* coeffs, size_t n, unsigned V, const uint
 void oracle_divide_out_points_acc(const uint64_t* coeffs, size_t n, unsigned V, const uint64_t* zs, const uint64_t* cs, unsigned k,
                                   unsigned PW, uint64_t* acc) {
     fq3 rem[64], z[64], c[64];
-    if (k > 64) return;
+    while (k > 64) {                                                   /* the sum over k is taken 64 terms at a time: any k */
+        oracle_divide_out_points_acc(coeffs, n, V, zs, cs, 64, PW, acc);
+        zs += (size_t)PW * 64; cs += (size_t)PW * 64; k -= 64;
+    }
     for (unsigned t = 0; t < k; t++) { rem[t] = (fq3){0, 0, 0}; z[t] = ld_q(zs + (size_t)PW * t, PW); c[t] = ld_q(cs + (size_t)PW * t, PW); }
     for (size_t i = n; i-- > 0;) {
         const fq3 tmp = ld_q(coeffs + (size_t)V * i, V);

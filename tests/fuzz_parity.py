@@ -2,7 +2,8 @@
 """Randomised differential run of the library against the C oracle (oracle/c) on the GPU:
     python tests/fuzz_parity.py [seconds] [seed]
 Random sizes (2^0 .. 2^21: every plan family incl. the (256, R, 256) ones), fields, directions, coset offsets, blow-ups, folding factors, shifts and column
-counts; the element-wise stages run through the C ABI at any length up to 2^15, not only powers of two; values are a mix of uniform elements and edge values (0, 1, p-1, 2^32-1, 2^32, p-2^32 ...).
+counts; the element-wise stages run through the C ABI at any length up to 2^15, not only powers of two; the DEEP entry points (ms_deep_rows, ms_deep_compose,
+ms_horner_eval) through the C ABI over all three fields with any number of points, 0..40 terms per point and any first / count up to 2^13; values are a mix of uniform elements and edge values (0, 1, p-1, 2^32-1, 2^32, p-2^32 ...).
 Complements tests/ (fixed shapes): any mismatch prints the failing case and exits non-zero.  MS_FUZZ_BACKEND=emu: the same on the simulator build
 (CPU; transforms to 2^18, LDEs to 2^14 rows)."""
 import sys
@@ -137,7 +138,69 @@ def case_stage():
     return bool(ok), f"stage n={n} fields=({VL},{VR}) shift={shift} e={e} const_op={op} ncols={ncols}"
 
 
-CASES = [case_ntt, case_lde, case_evaluate, case_fri, case_commit, case_stage]
+def case_deep():
+    # the DEEP entry points through the C ABI (tests/deep_ref.py: the references of tests/test_deep_sweep.py): any field, any number of points,
+    # 0..40 terms per point, any first / count up to 2^13, edge words at a drawn density
+    from tests import deep_ref as D
+    f = [D.FP, D.FQ3, D.F252][int(rng.integers(0, 3))]
+    entry = ["rows", "compose", "horner"][int(rng.integers(0, 3))]
+    npoints, density, seed = int(rng.integers(1, 9)), float(rng.choice([0.0, 0.1, 0.3, 0.9])), int(rng.integers(1 << 30))
+    counts = [int(rng.integers(0, 41)) for _ in range(npoints)]
+    nbase, next_ = int(rng.integers(0 if f == D.FQ3 else 1, 6)), (int(rng.integers(0, 4)) if f == D.FQ3 else 0)
+    if nbase + next_ == 0:
+        nbase = 1
+    offset, degree = [None, 1, "other"][int(rng.integers(0, 3))], ["rand", "b0", "a0", "one"][int(rng.integers(0, 4))]
+    kinds = tuple(str(k) for k in rng.choice(["rand", "zero", "base", "x"] if f == D.FQ3 else ["rand", "zero"], size=2, replace=False))
+    bf = D.F252 if f == D.F252 else D.FP
+    what = f"deep {entry} field={f} npoints={npoints} counts={counts} nbase={nbase} next={next_} offset={offset} degree={degree} density={density} seed={seed}"
+    try:
+        if entry == "rows":
+            ld = int(rng.integers(1, 15))
+            N = 1 << ld
+            count = int(rng.integers(1, min(N, 1 << 13) + 1))
+            first = int(rng.integers(0, N - count + 1))
+            what += f" log_domain={ld} first={first} count={count}"
+            h, _ = D.offset_of(f, offset)
+            base = [D.column(bf, count, "mix", seed + c, density) for c in range(nbase)]
+            ext = [D.column(D.FQ3, count, "mix", seed + 10 + c, density) for c in range(next_)]
+            tcol, tpoint, alpha, ood = D.terms_of(f, counts, nbase + next_, None, seed + 50, density)
+            points = D.points_of(f, npoints, kinds, h, N, seed + 60)
+            da, db = D.degree_of(f, degree, seed + 70)
+            D.check_rows(pl, f, ld, first, count, offset, base, ext, points, tcol, tpoint, alpha, ood, da, db, seed, what)
+        elif entry == "compose":
+            log_n = int(rng.integers(0, 12 if f == D.F252 else 14))
+            n = 1 << log_n
+            what += f" log_n={log_n}"
+            h, off = D.offset_of(f, offset)
+            base = [D.column(bf, n, "mix", seed + c, density) for c in range(nbase)]
+            ext = [D.column(D.FQ3, n, "mix", seed + 10 + c, density) for c in range(next_)]
+            tcol, tpoint, alpha, _ = D.terms_of(f, counts, nbase + next_, None, seed + 50, density)
+            points = D.points_of(f, npoints, kinds, h, n, seed + 60)
+            da, db = D.degree_of(f, degree, seed + 70)
+            ood = D.oods_252(base, points, tcol, tpoint) if f == D.F252 else D.oods_gl(f, base, ext, points, tcol, tpoint)
+            B, E, out = [D.Buf(pl, w) for w in base], [D.Buf(pl, w) for w in ext], D.Buf.junk(pl, n * D.PW[f])
+            assert D.call_deep(pl, "compose", f, (log_n, off), B, E, points, tcol, tpoint, alpha, ood, da, db, out.ptr) == 0, pl.lib.ms_last_error().decode()
+            pl.sync()
+            if f != D.F252:
+                D.same(out.read(), D.ref_compose_gl(f, n, base, ext, points, tcol, tpoint, alpha, da, db), what)
+            elif log_n <= 7:
+                D.same(out.read(), D.ref_compose_252_division(n, base, points, tcol, tpoint, alpha, da, db), what)
+            elif not any(D.on_coset(f, points[4 * k:4 * k + 4], 5, n) for k in range(npoints)):
+                D.check_compose_252_identity(log_n, out.read(), base, points, tcol, tpoint, alpha, ood, da, db)
+        else:
+            cf, pf = [(D.FP, D.FP), (D.FP, D.FQ3), (D.FQ3, D.FQ3), (D.F252, D.F252)][int(rng.integers(0, 4))]
+            n = int(rng.integers(0, (1 << 13) + 1))
+            ncols = int(rng.integers(1, 7))
+            qcol = sorted(int(c) for c in rng.integers(0, ncols, size=int(rng.integers(0, 12)))) + [int(c) for c in rng.integers(0, ncols, size=3)]
+            what = f"deep horner fields=({cf},{pf}) n={n} qcol={qcol} density={density} seed={seed}"
+            cols = [D.column(cf, n, "mix", seed + c, density) for c in range(ncols)]
+            D.check_horner(pl, cf, pf, n, cols, qcol, D.words(pf, len(qcol), seed + 9, density), what=what)
+    except AssertionError as e:
+        return False, what + ": " + str(e)[:300]
+    return True, what
+
+
+CASES = [case_ntt, case_lde, case_evaluate, case_fri, case_commit, case_stage, case_deep]
 t0, count = time.time(), 0
 while time.time() - t0 < budget:
     fn = CASES[int(rng.integers(0, len(CASES)))]
