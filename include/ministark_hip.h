@@ -12,8 +12,14 @@
  *     Every element handed in -- columns, constants, challenges, offsets -- must be
  *     CANONICAL (< p), as every value of the reference's field types is (ark-ff keeps
  *     residues reduced): the kernels' unreduced accumulators are sized for canonical
- *     operands, a word in [p, 2^64) or a 252-bit value in [p, 2^256) gives a wrong
- *     (not a rejected) result.  Every element handed back is canonical.
+ *     operands.  By default this is the caller's duty and is not looked at: a word in
+ *     [p, 2^64) or a 252-bit value in [p, 2^256) gives a wrong (not a rejected) result.
+ *     A binding without such a type system can have it checked: ms_check_canonical scans
+ *     columns on the device and reports the first offending (column, row, component), and
+ *     in CHECKED MODE (ms_ctx_set_checked, or MS_CHECK_CANONICAL=1 in the environment)
+ *     every entry point that does arithmetic on field data refuses non-canonical input
+ *     with MS_ERR_INVALID before anything is enqueued -- see "checked mode" below.
+ *     Every element handed back is canonical.
  *   - `void* d_*` are DEVICE pointers (hipMalloc / ms_alloc / a torch tensor's
  *     data_ptr); `const void* h_*` are small HOST constants (one field element).
  *   - Every function returns 0 on success, a negative MS_ERR_* otherwise, and
@@ -67,6 +73,47 @@ size_t ms_field_bytes(int field);              /* 8 / 24 / 32 */
  * "kernel_name calls total_microseconds algorithmic_bytes_per_call". */
 int ms_profile_enable(ms_ctx* ctx, int on);
 int ms_profile_read(ms_ctx* ctx, char* buf, size_t cap);
+
+/* ---- checked mode: the canonical-input rule of "Conventions", enforced (no counterpart in the reference, whose field types cannot hold
+ * an unreduced residue).  An element is canonical when the integer it stores is < p: a Goldilocks word < 2^64 - 2^32 + 1 (all three
+ * components of an Fq3 element), the four little-endian limbs of an Fp252 element < 2^251 + 17 * 2^192 + 1.
+ * ms_check_canonical       scans `ncols` columns of `n` elements of `field` in one read-only launch at the rate the device streams reads.
+ *                          Blocks; returns MS_OK whatever it finds -- the finding is the report.  Any n and ncols (n = 0 or ncols = 0: count
+ *                          0, no launch); columns may alias each other and need only element alignment; nothing is written to a column.
+ *                          MS_ERR_INVALID: unknown field, null table with ncols > 0, null column with n > 0, null out.
+ * ms_check_canonical_host  the same rule over `count` packed host elements; *first_bad = the index of the first non-canonical one, or
+ *                          `count` when there is none.  Needs no context and no device.
+ * ms_ctx_set_checked       switches checked mode on or off (default: off, or on when MS_CHECK_CANONICAL=1 is in the environment at
+ *                          ms_ctx_create).  Off: nothing changes -- same launches, same words, same return codes.  On: an entry point of
+ *                          the list below first scans its device inputs (ms_check_canonical) and host constants
+ *                          (ms_check_canonical_host); on the first non-canonical element it returns MS_ERR_INVALID with ms_last_error() =
+ *                          "<entry>: <argument> holds an element that is not canonical (>= p): column C, row R[, component K]; ...",
+ *                          before anything is enqueued and before any buffer is written, in-place forms included.  (Host arrays count as
+ *                          column 0, row = element index; a row-major matrix reports its own row and column.)  With clean input the call
+ *                          then runs as usual and produces the words it produces unchecked.  A checked call BLOCKS -- the scan's
+ *                          result is read back before the work is enqueued -- also where the entry point is documented asynchronous:
+ *                          a diagnostic mode, like MS_EVAL_SELFCHECK.
+ *   checked:      ms_ntt_plan_create (h_offset, h_group_gen), ms_ntt_encode / ms_ntt_execute / ms_ntt_enqueue / ms_ntt_enqueue_to (the
+ *                 columns, no later than the launch that would read them), ms_lde, ms_evaluate, ms_binary, ms_binary_const, ms_mul_pow,
+ *                 ms_unary, ms_convert, ms_fill, ms_sum_columns, ms_sha256_rows[_row_major], ms_blake2s_rows[_row_major],
+ *                 ms_rpo256_rows[_row_major | _field], ms_rpo256_merkle (its leaves are Fp elements), ms_eval_program[_ex],
+ *                 ms_validate_constraints (columns, d_x_lde, h_domain_offset, the constant words), ms_scan_affine, ms_fri_fold[_rows],
+ *                 ms_horner_eval, ms_deep_rows, ms_deep_compose (columns, points, alphas, OOD values, the degree pair, h_offset).
+ *   NOT checked:  entry points that only move words -- ms_copy, ms_upload, ms_download, ms_bit_reverse, ms_deinterleave, ms_gather_rows,
+ *                 ms_gather_digests[_multi], the byte-digest merkle builders (ms_sha256_merkle, ms_blake2s_merkle), the proof-of-work
+ *                 grinders and the RCCL exchange. */
+typedef struct ms_canon_report {
+    uint64_t count;      /* ELEMENTS that are not canonical (an Fq3 element with two bad components counts once) */
+    uint64_t first_row;  /* valid when count > 0 */
+    uint32_t first_col;  /* smallest column index that holds one; first_row is the smallest row within that column */
+    uint32_t first_word; /* index, within that element, of the first offending component (Fq3: 0..2; Fp, Fp252: 0) */
+} ms_canon_report;
+/* `out` points at a ms_canon_report; it is declared void* (as h_id128 and the other caller-owned records are) so that bindings generated
+ * from this header need no pointer type of their own -- C and C++ callers pass &report. */
+int ms_check_canonical(ms_ctx* ctx, int field, size_t n, const void* const* d_cols, unsigned ncols, void* out);
+int ms_check_canonical_host(int field, const void* h_elems, size_t count, size_t* first_bad);
+int ms_ctx_set_checked(ms_ctx* ctx, int on);
+int ms_ctx_get_checked(ms_ctx* ctx, int* on);
 
 /* ---- memory: GpuAllocator + buffer_no_copy (src/utils.rs:438-470, gpu/src/utils.rs:103-134).
  * The reference aliases page-aligned host Vecs (unified memory); on a discrete GPU

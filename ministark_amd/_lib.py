@@ -29,6 +29,19 @@ class JitStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CanonReport(ctypes.Structure):
+    """`ms_canon_report` of include/ministark_hip.h: what ms_check_canonical found."""
+    _fields_ = [("count", ctypes.c_uint64), ("first_row", ctypes.c_uint64), ("first_col", ctypes.c_uint32), ("first_word", ctypes.c_uint32)]
+
+    def __bool__(self):
+        return self.count == 0                   # true when every element is canonical
+
+    def __repr__(self):
+        if not self.count:
+            return "CanonReport(count=0)"
+        return f"CanonReport(count={self.count}, first_col={self.first_col}, first_row={self.first_row}, first_word={self.first_word})"
+
+
 class Lib:
     """Typed view of the C ABI in include/ministark_hip.h."""
 
@@ -51,6 +64,10 @@ class Lib:
             "ms_field_bytes": (sz, [i]),
             "ms_profile_enable": (i, [vp, i]),
             "ms_profile_read": (i, [vp, ctypes.c_char_p, sz]),
+            "ms_check_canonical": (i, [vp, i, sz, c_void_pp, u, vp]),
+            "ms_check_canonical_host": (i, [i, vp, sz, ctypes.POINTER(sz)]),
+            "ms_ctx_set_checked": (i, [vp, i]),
+            "ms_ctx_get_checked": (i, [vp, ctypes.POINTER(i)]),
             "ms_alloc": (i, [vp, sz, c_void_pp]),
             "ms_free": (i, [vp, vp]),
             "ms_copy": (i, [vp, vp, vp, sz]),

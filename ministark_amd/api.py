@@ -84,6 +84,19 @@ class Planner:
                          "bytes_per_call": float(b)}
         return out
 
+    def checked(self, on=True):
+        """Checked mode (ms_ctx_set_checked): every call that does arithmetic on field data first scans its inputs for non-canonical
+        elements (>= p) and raises MsError, naming argument, column and row, before anything is enqueued.  Checked calls block: a
+        diagnostic mode.  Returns the planner, so that `Planner().checked()` reads well."""
+        self.lib.check(self.lib.ms_ctx_set_checked(self.handle, 1 if on else 0))
+        return self
+
+    @property
+    def is_checked(self):
+        on = ctypes.c_int(0)
+        self.lib.check(self.lib.ms_ctx_get_checked(self.handle, ctypes.byref(on)))
+        return bool(on.value)
+
     def jit_stats(self):
         """-> dict: this context's specialised constraint kernels -- compiled, loaded from the on-disk cache, failed (interpreter) -- and
         what that cost in milliseconds.  A non-zero `compile_failures` is a performance bug worth reporting, never a wrong result."""
@@ -474,6 +487,21 @@ def _ptr_array(vecs):
     return (ctypes.c_void_p * len(vecs))(*[v.ptr for v in vecs])
 
 
+def check_canonical(planner, cols, field=None):
+    """ms_check_canonical over equally long columns (GpuVecs, a ColumnSet or a Matrix) -> _lib.CanonReport: `count` elements are not
+    canonical; when count > 0, `first_col` / `first_row` / `first_word` locate the first one (smallest column, then smallest row; the
+    component within an Fq3 element).  The report is truthy when everything is canonical.  Blocks; writes nothing."""
+    cols = cols.columns if isinstance(cols, (Matrix, ColumnSet)) else list(cols)
+    rep = _lib.CanonReport()
+    if not cols:
+        return rep
+    field = cols[0].field if field is None else field
+    if any(len(c) != len(cols[0]) or c.field != field for c in cols):
+        raise ValueError("all columns of a scan must have the same length and field")
+    planner.lib.check(planner.lib.ms_check_canonical(planner.handle, field, len(cols[0]), _ptr_array(cols), len(cols), ctypes.byref(rep)))
+    return rep
+
+
 class ColumnSet:
     """A fixed list of equally long columns of one field with its pointer table built ONCE: what `enqueue` / `enqueue_to` take when the same
     columns are transformed again and again (building the table of 512 pointers and checking 512 lengths in the interpreter costs more than
@@ -616,6 +644,10 @@ class Matrix:
 
     def to_numpy(self):
         return [c.to_numpy() for c in self.columns]
+
+    def check_canonical(self):
+        """-> the report of ms_check_canonical over the columns (see check_canonical)."""
+        return check_canonical(self.planner, self.columns) if self.columns else _lib.CanonReport()
 
     # src/matrix.rs:102-116 (into_polynomials_gpu) ------------------------------------
     def into_polynomials(self, domain):

@@ -57,6 +57,10 @@ public:
     void sync() const { check(ms_sync(ctx_)); }        // command_buffer.wait_until_completed()
     // specialised constraint kernels of this context: compiled / loaded from the on-disk cache / left to the interpreter (include/ministark_hip.h)
     ms_jit_stats jit_stats() const { ms_jit_stats st{}; check(ms_eval_jit_stats(ctx_, &st)); return st; }
+    // checked mode (include/ministark_hip.h): every call that does arithmetic on field data first scans its inputs for non-canonical elements and
+    // throws (MS_ERR_INVALID: argument, column, row) before anything is enqueued.  Checked calls block: a diagnostic mode.
+    void set_checked(bool on) { check(ms_ctx_set_checked(ctx_, on ? 1 : 0)); }
+    bool checked() const { int on = 0; check(ms_ctx_get_checked(ctx_, &on)); return on != 0; }
 private:
     ms_ctx* ctx_ = nullptr;
 };
@@ -222,6 +226,14 @@ public:
     size_t num_cols() const { return columns.size(); }
     Planner& planner() const { return columns.at(0).planner(); }
     Matrix clone() const { Matrix m; for (auto& c : columns) m.columns.push_back(c.clone()); return m; }
+    // ms_check_canonical over the columns: how many elements are not canonical (>= p) and where the first one is (blocks; writes nothing)
+    ms_canon_report check_canonical() const {
+        ms_canon_report r{};
+        if (columns.empty()) return r;
+        std::vector<const void*> in; for (auto& c : columns) in.push_back(c.ptr());
+        check(ms_check_canonical(planner().ctx(), F::id, num_rows(), in.data(), (unsigned)in.size(), &r));
+        return r;
+    }
     Matrix& into_polynomials(const Radix2EvaluationDomain& d) {       // src/matrix.rs:102-116
         GpuIfft<F> ifft(planner(), d);
         ifft.enqueue(columns);                                         // encode + execute without the wait

@@ -26,6 +26,7 @@ extern "C" int ms_blake2s_rows(ms_ctx* ctx, int field, size_t nrows, const void*
     for (unsigned c = 0; c < ncols; c++)
         if (!d_cols[c]) return fail(MS_ERR_INVALID, "ms_blake2s_rows: null column %u", c);
     if (nrows == 0) return MS_OK;
+    MSCHK(canon_cols(ctx, "ms_blake2s_rows", "d_cols", field, nrows, d_cols, ncols));
     msb2s::RowsParams P;
     memset(&P, 0, sizeof P);
     for (unsigned c = 0; c < ncols; c++) P.cols[c] = (const uint64_t*)d_cols[c];
@@ -39,6 +40,7 @@ extern "C" int ms_blake2s_rows_row_major(ms_ctx* ctx, int field, size_t nrows, u
     MSCHK(field_words(field, &V));
     if (ncols == 0 || ncols > (unsigned)msb2s::MAXCOLS) return fail(MS_ERR_UNSUPPORTED, "1..%d columns per row", msb2s::MAXCOLS);
     if (nrows == 0) return MS_OK;
+    MSCHK(canon_rows(ctx, "ms_blake2s_rows_row_major", "d_matrix", field, nrows, ncols, d_matrix));
     msb2s::RowsParams P;
     memset(&P, 0, sizeof P);
     for (unsigned c = 0; c < ncols; c++) P.cols[c] = (const uint64_t*)d_matrix + (size_t)c * V;

@@ -61,6 +61,7 @@ extern "C" int ms_ctx_create(int device, ms_ctx** out) {
     if (e != hipSuccess) { delete ctx; return fail(MS_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
     if (const char* g = getenv("MS_NTT_GROUP_BYTES")) ctx->group_bytes = (size_t)strtoull(g, nullptr, 10);
     if (const char* g = getenv("MS_POOL_BYTES")) ctx->pool_cap = (size_t)strtoull(g, nullptr, 10);
+    if (const char* g = getenv("MS_CHECK_CANONICAL")) ctx->checked = !strcmp(g, "1");
     *out = ctx;
     return MS_OK;
 }

@@ -22,6 +22,20 @@ static int out_overlaps_no_column(const char* entry, const void* d_out, size_t o
             return fail(MS_ERR_INVALID, "%s: d_out and %s column %u overlap (the output must be disjoint from every input column)", entry, kind, c);
     return MS_OK;
 }
+// checked mode: every host constant and every column of a DEEP call, after the shape checks and before anything else looks at the values
+static int deep_canon(ms_ctx* ctx, const char* entry, int point_field, const void* h_offset, size_t n, const void* const* d_base, const char* base_name,
+                      unsigned nbase, const void* const* d_ext, const char* ext_name, unsigned next, const void* h_points, unsigned npoints,
+                      const void* h_term_alpha, const void* h_term_ood, unsigned nterms, const void* h_degree_alpha, const void* h_degree_beta) {
+    const int bf = point_field == MS_STARK252_FP ? MS_STARK252_FP : MS_GOLDILOCKS_FP;
+    MSCHK(canon_host(ctx, entry, "h_offset", bf, h_offset, 1));
+    MSCHK(canon_host(ctx, entry, "h_points", point_field, h_points, npoints));
+    MSCHK(canon_host(ctx, entry, "h_term_alpha", point_field, h_term_alpha, nterms));
+    MSCHK(canon_host(ctx, entry, "h_term_ood", point_field, h_term_ood, nterms));
+    MSCHK(canon_host(ctx, entry, "h_degree_alpha", point_field, h_degree_alpha, 1));
+    MSCHK(canon_host(ctx, entry, "h_degree_beta", point_field, h_degree_beta, 1));
+    MSCHK(canon_cols(ctx, entry, base_name, bf, n, d_base, nbase));
+    return canon_cols(ctx, entry, ext_name, point_field, n, d_ext, next);
+}
 static gl::Fq3 q3_load(const uint64_t* p, unsigned PW) { return PW == 3 ? gl::Fq3{p[0], p[1], p[2]} : gl::Fq3{p[0], 0, 0}; }
 
 // ---- the 252-bit instantiations (Fq = Fp = Fp252)
@@ -30,6 +44,8 @@ static int horner_eval252(ms_ctx* ctx, size_t n, const void* const* d_cols, unsi
     if (ncols > (unsigned)msdeep::MAXCOLS) return fail(MS_ERR_UNSUPPORTED, "at most %d columns per call", msdeep::MAXCOLS);
     if (nq == 0) return MS_OK;
     for (unsigned q = 0; q < nq; q++) if (h_qcol[q] >= ncols) return fail(MS_ERR_INVALID, "query %u names column %u of %u", q, h_qcol[q], ncols);
+    MSCHK(canon_host(ctx, "ms_horner_eval", "h_qpoints", MS_STARK252_FP, h_qpoints, nq));
+    MSCHK(canon_cols(ctx, "ms_horner_eval", "d_cols", MS_STARK252_FP, n, d_cols, ncols));
     const unsigned nblocks = (unsigned)std::max<size_t>(1, (n + 4095) / 4096);
     void *d_qcol = nullptr, *d_pts = nullptr, *d_part = nullptr;
     PoolGuard pooled(ctx);                                 // temporaries go back to the pool on every exit path
@@ -77,6 +93,8 @@ static int deep_compose252(ms_ctx* ctx, unsigned log_n, const void* h_offset, co
     if (log_n > 40) return fail(MS_ERR_INVALID, "log_n too large");
     for (unsigned t = 0; t < nterms; t++)
         if (h_term_col[t] >= ncols || h_term_point[t] >= npoints) return fail(MS_ERR_INVALID, "term %u out of range", t);
+    MSCHK(deep_canon(ctx, "ms_deep_compose", MS_STARK252_FP, h_offset, (size_t)1 << log_n, d_polys, "d_base_polys", ncols, nullptr, "d_ext_polys", 0, h_points, npoints,
+                     h_term_alpha, h_term_ood, nterms, h_degree_alpha, h_degree_beta));
     f252::E h = f252::to_mont(f252::E{{3, 0, 0, 0}});          // the field's generator (gpu/src/fields.rs:241)
     if (h_offset) memcpy(h.l, h_offset, 32);
     if (f252::is_zero(h) || f252::geq_p(h)) return fail(MS_ERR_INVALID, "coset offset must be a non-zero canonical element");
@@ -151,6 +169,8 @@ static int deep_rows252(ms_ctx* ctx, unsigned log_domain, const void* h_offset, 
     if (first > N || count > N - first) return fail(MS_ERR_INVALID, "ms_deep_rows: rows [%zu, %zu) outside the domain", first, first + count);
     for (unsigned t = 0; t < nterms; t++)
         if (h_term_col[t] >= ncols || h_term_point[t] >= npoints) return fail(MS_ERR_INVALID, "term %u out of range", t);
+    MSCHK(deep_canon(ctx, "ms_deep_rows", MS_STARK252_FP, h_offset, count, d_rows, "d_base_rows", ncols, nullptr, "d_ext_rows", 0, h_points, npoints,
+                     h_term_alpha, h_term_ood, nterms, h_degree_alpha, h_degree_beta));
     f252::E h = f252::to_mont(f252::E{{3, 0, 0, 0}});          // the field's generator, as deep_compose252
     if (h_offset) memcpy(h.l, h_offset, 32);
     if (f252::is_zero(h) || f252::geq_p(h)) return fail(MS_ERR_INVALID, "coset offset must be a non-zero canonical element");
@@ -229,6 +249,8 @@ extern "C" int ms_horner_eval(ms_ctx* ctx, int coeff_field, int point_field, siz
     if (ncols > (unsigned)msdeep::MAXCOLS) return fail(MS_ERR_UNSUPPORTED, "at most %d columns per call", msdeep::MAXCOLS);
     if (nq == 0) return MS_OK;
     for (unsigned q = 0; q < nq; q++) if (h_qcol[q] >= ncols) return fail(MS_ERR_INVALID, "query %u names column %u of %u", q, h_qcol[q], ncols);
+    MSCHK(canon_host(ctx, "ms_horner_eval", "h_qpoints", point_field, h_qpoints, nq));
+    MSCHK(canon_cols(ctx, "ms_horner_eval", "d_cols", coeff_field, n, d_cols, ncols));
     if (n == 0) { memset(h_out, 0, (size_t)nq * PW * 8); return MS_OK; }           // the zero polynomial
     // queries on the same column that follow one another (the callers list them per column) share one pass over the coefficients
     constexpr unsigned GQ = 2;
@@ -348,6 +370,8 @@ extern "C" int ms_deep_compose(ms_ctx* ctx, int point_field, unsigned log_n, con
     if (log_n > 32) return fail(MS_ERR_INVALID, "log_n too large");
     for (unsigned t = 0; t < nterms; t++)
         if (h_term_col[t] >= nbase + next || h_term_point[t] >= npoints) return fail(MS_ERR_INVALID, "term %u out of range", t);
+    MSCHK(deep_canon(ctx, "ms_deep_compose", point_field, h_offset, (size_t)1 << log_n, d_base_polys, "d_base_polys", nbase, d_ext_polys, "d_ext_polys", next,
+                     h_points, npoints, h_term_alpha, h_term_ood, nterms, h_degree_alpha, h_degree_beta));
     uint64_t h = gl::GENERATOR;
     if (h_offset) { uint64_t h_m; memcpy(&h_m, h_offset, 8); h = gl::from_mont(h_m); }
     if (h == 0) return fail(MS_ERR_INVALID, "coset offset must be non-zero");
@@ -481,6 +505,8 @@ extern "C" int ms_deep_rows(ms_ctx* ctx, int point_field, unsigned log_domain, c
     if (first > N || count > N - first) return fail(MS_ERR_INVALID, "ms_deep_rows: rows [%zu, %zu) outside the domain", first, first + count);
     for (unsigned t = 0; t < nterms; t++)
         if (h_term_col[t] >= nbase + next || h_term_point[t] >= npoints) return fail(MS_ERR_INVALID, "term %u out of range", t);
+    MSCHK(deep_canon(ctx, "ms_deep_rows", point_field, h_offset, count, d_base_rows, "d_base_rows", nbase, d_ext_rows, "d_ext_rows", next,
+                     h_points, npoints, h_term_alpha, h_term_ood, nterms, h_degree_alpha, h_degree_beta));
     uint64_t h = gl::GENERATOR;
     if (h_offset) { uint64_t h_m; memcpy(&h_m, h_offset, 8); h = gl::from_mont(h_m); }
     if (h == 0) return fail(MS_ERR_INVALID, "coset offset must be non-zero");

@@ -18,13 +18,18 @@
 // ---------------------------------------------------------------------------------------
 // fused constraint evaluation
 // ---------------------------------------------------------------------------------------
+static int eval_entry(const char* entry, ms_ctx* ctx, const uint32_t* h_prog, unsigned ninstr, const void* h_consts, unsigned nconst_words,
+                      unsigned log_n, unsigned lde_step, const void* h_domain_offset, const void* d_x_lde,
+                      const void* const* d_base_cols, unsigned nbase, const void* const* d_ext_cols, unsigned next,
+                      const void* const* d_periodic, const unsigned* periodic_len, unsigned nperiodic,
+                      int out_field, void* d_out, unsigned flags);
 extern "C" int ms_eval_program(ms_ctx* ctx, const uint32_t* h_prog, unsigned ninstr, const void* h_consts, unsigned nconst_words,
                                unsigned log_n, unsigned lde_step, const void* h_domain_offset, const void* d_x_lde,
                                const void* const* d_base_cols, unsigned nbase, const void* const* d_ext_cols, unsigned next,
                                const void* const* d_periodic, const unsigned* periodic_len, unsigned nperiodic,
                                int out_field, void* d_out) {
-    return ms_eval_program_ex(ctx, h_prog, ninstr, h_consts, nconst_words, log_n, lde_step, h_domain_offset, d_x_lde, d_base_cols, nbase,
-                              d_ext_cols, next, d_periodic, periodic_len, nperiodic, out_field, d_out, 0u);
+    return eval_entry("ms_eval_program", ctx, h_prog, ninstr, h_consts, nconst_words, log_n, lde_step, h_domain_offset, d_x_lde, d_base_cols, nbase,
+                      d_ext_cols, next, d_periodic, periodic_len, nperiodic, out_field, d_out, 0u);
 }
 static int eval_locked(ms_ctx* ctx, const uint32_t* h_prog, unsigned ninstr, const void* h_consts, unsigned nconst_words,
                        unsigned log_n, unsigned lde_step, const void* h_domain_offset, const void* d_x_lde,
@@ -37,7 +42,17 @@ extern "C" int ms_eval_program_ex(ms_ctx* ctx, const uint32_t* h_prog, unsigned 
                                   const void* const* d_base_cols, unsigned nbase, const void* const* d_ext_cols, unsigned next,
                                   const void* const* d_periodic, const unsigned* periodic_len, unsigned nperiodic,
                                   int out_field, void* d_out, unsigned flags) {
+    return eval_entry("ms_eval_program_ex", ctx, h_prog, ninstr, h_consts, nconst_words, log_n, lde_step, h_domain_offset, d_x_lde, d_base_cols, nbase,
+                      d_ext_cols, next, d_periodic, periodic_len, nperiodic, out_field, d_out, flags);
+}
+static int eval_entry(const char* entry, ms_ctx* ctx, const uint32_t* h_prog, unsigned ninstr, const void* h_consts, unsigned nconst_words,
+                      unsigned log_n, unsigned lde_step, const void* h_domain_offset, const void* d_x_lde,
+                      const void* const* d_base_cols, unsigned nbase, const void* const* d_ext_cols, unsigned next,
+                      const void* const* d_periodic, const unsigned* periodic_len, unsigned nperiodic,
+                      int out_field, void* d_out, unsigned flags) {
     if (!ctx) return fail(MS_ERR_INVALID, "ms_eval_program: null argument");
+    MSCHK(canon_program(ctx, entry, out_field == MS_STARK252_FP, h_prog, ninstr, h_consts, nconst_words, log_n, h_domain_offset, d_x_lde,
+                        d_base_cols, nbase, d_ext_cols, next, d_periodic, periodic_len, nperiodic));
     std::lock_guard<std::mutex> lk(ctx->mu);
     MSCHK(eval_locked(ctx, h_prog, ninstr, h_consts, nconst_words, log_n, lde_step, h_domain_offset, d_x_lde, d_base_cols, nbase, d_ext_cols, next,
                       d_periodic, periodic_len, nperiodic, out_field, d_out, flags));

@@ -13,6 +13,7 @@ extern "C" int ms_sha256_rows(ms_ctx* ctx, int field, size_t nrows, const void* 
     MSCHK(field_words(field, &V));
     if (ncols > (unsigned)mssha::MAXCOLS) return fail(MS_ERR_UNSUPPORTED, "at most %d columns per commitment", mssha::MAXCOLS);
     if (nrows == 0) return MS_OK;
+    MSCHK(canon_cols(ctx, "ms_sha256_rows", "d_cols", field, nrows, d_cols, ncols));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     mssha::RowsParams P;
@@ -33,6 +34,7 @@ extern "C" int ms_sha256_rows_row_major(ms_ctx* ctx, int field, size_t nrows, un
     MSCHK(field_words(field, &V));
     if (ncols == 0 || ncols > (unsigned)mssha::MAXCOLS) return fail(MS_ERR_UNSUPPORTED, "1..%d columns per row", mssha::MAXCOLS);
     if (nrows == 0) return MS_OK;
+    MSCHK(canon_rows(ctx, "ms_sha256_rows_row_major", "d_matrix", field, nrows, ncols, d_matrix));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     mssha::RowsParams P;
@@ -103,6 +105,7 @@ static int rpo_rows(ms_ctx* ctx, size_t nrows, const uint64_t* const* cols, unsi
 }
 extern "C" int ms_rpo256_rows(ms_ctx* ctx, size_t nrows, const void* const* d_cols, unsigned ncols, void* d_digests) {
     if (!ctx || !d_cols || !d_digests) return fail(MS_ERR_INVALID, "ms_rpo256_rows: null argument");
+    if (ncols && ncols <= (unsigned)msrpo::MAXCOLS) MSCHK(canon_cols(ctx, "ms_rpo256_rows", "d_cols", MS_GOLDILOCKS_FP, nrows, d_cols, ncols));
     std::vector<const uint64_t*> cols(ncols);
     for (unsigned c = 0; c < ncols; c++) cols[c] = (const uint64_t*)d_cols[c];
     return rpo_rows(ctx, nrows, cols.data(), ncols, 1, d_digests);
@@ -114,6 +117,7 @@ extern "C" int ms_rpo256_rows_field(ms_ctx* ctx, int field, size_t nrows, const 
     unsigned V = 0;
     MSCHK(field_words(field, &V));
     if (V != 1 && V != 3) return fail(MS_ERR_UNSUPPORTED, "RPO-256 absorbs Goldilocks elements (Fp or Fq3 columns)");
+    if (ncols && ncols * V <= (unsigned)msrpo::MAXCOLS) MSCHK(canon_cols(ctx, "ms_rpo256_rows_field", "d_cols", field, nrows, d_cols, ncols));
     std::vector<const uint64_t*> cols;
     for (unsigned c = 0; c < ncols; c++) {
         if (!d_cols[c]) return fail(MS_ERR_INVALID, "null column %u", c);
@@ -123,6 +127,7 @@ extern "C" int ms_rpo256_rows_field(ms_ctx* ctx, int field, size_t nrows, const 
 }
 extern "C" int ms_rpo256_rows_row_major(ms_ctx* ctx, size_t nrows, unsigned ncols, const void* d_matrix, void* d_digests) {
     if (!ctx || !d_matrix || !d_digests) return fail(MS_ERR_INVALID, "ms_rpo256_rows_row_major: null argument");
+    if (ncols && ncols <= (unsigned)msrpo::MAXCOLS) MSCHK(canon_rows(ctx, "ms_rpo256_rows_row_major", "d_matrix", MS_GOLDILOCKS_FP, nrows, ncols, d_matrix));
     std::vector<const uint64_t*> cols(ncols);
     for (unsigned c = 0; c < ncols; c++) cols[c] = (const uint64_t*)d_matrix + c;
     return rpo_rows(ctx, nrows, cols.data(), ncols, ncols, d_digests);
@@ -130,6 +135,7 @@ extern "C" int ms_rpo256_rows_row_major(ms_ctx* ctx, size_t nrows, unsigned ncol
 extern "C" int ms_rpo256_merkle(ms_ctx* ctx, size_t nleaves, const void* d_leaves, void* d_nodes) {
     if (!ctx || !d_leaves || !d_nodes) return fail(MS_ERR_INVALID, "ms_rpo256_merkle: null argument");
     if (nleaves < 2 || (nleaves & (nleaves - 1))) return fail(MS_ERR_INVALID, "number of leaves must be a power of two >= 2");
+    MSCHK(canon_rows(ctx, "ms_rpo256_merkle", "d_leaves", MS_GOLDILOCKS_FP, nleaves, 4, d_leaves));      // a digest is a row of four Fp elements
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     uint64_t* nodes = (uint64_t*)d_nodes;

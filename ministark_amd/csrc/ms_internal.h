@@ -85,6 +85,9 @@ struct ms_ctx {
     JitStats jit_stats;
     // optional per-launch timing (ms_profile_*): hipEvent pairs around every kernel launch
     bool profiling = false;
+    // checked mode (ms_ctx_set_checked; MS_CHECK_CANONICAL=1 at ms_ctx_create): every entry point that does arithmetic on field data scans
+    // its inputs for non-canonical elements first (ms_canon.cpp) and refuses before anything is enqueued
+    bool checked = false;
     struct ProfRec { const char* name; hipEvent_t e0, e1; double bytes; };
     std::vector<ProfRec> prof;
 };
@@ -183,6 +186,17 @@ struct ms_ntt_plan {
     uint64_t* d252_twr[3] = {nullptr, nullptr, nullptr};
 };
 
+
+// ms_canon.cpp: the checks of the checked mode.  Called WITHOUT ctx->mu, after the entry point's own argument checks and before anything is
+// enqueued; MS_OK at once when the mode is off.  `arg` is the argument's name as include/ministark_hip.h spells it.
+int canon_cols(ms_ctx* ctx, const char* entry, const char* arg, int field, size_t n, const void* const* d_cols, unsigned ncols);
+int canon_col(ms_ctx* ctx, const char* entry, const char* arg, int field, size_t n, const void* d_col);
+int canon_rows(ms_ctx* ctx, const char* entry, const char* arg, int field, size_t nrows, unsigned ncols, const void* d_matrix);   // row-major matrix
+int canon_host(ms_ctx* ctx, const char* entry, const char* arg, int field, const void* h_elems, size_t count);
+int canon_program(ms_ctx* ctx, const char* entry, bool is252, const uint32_t* h_prog, unsigned ninstr, const void* h_consts, unsigned nconst_words,
+                  unsigned log_n, const void* h_domain_offset, const void* d_x_lde, const void* const* d_base_cols, unsigned nbase,
+                  const void* const* d_ext_cols, unsigned next, const void* const* d_periodic, const unsigned* periodic_len, unsigned nperiodic);
+static inline int field_of_words(unsigned V) { return V == 1 ? MS_GOLDILOCKS_FP : V == 3 ? MS_GOLDILOCKS_FQ3 : MS_STARK252_FP; }
 
 // ms_ntt.cpp
 int ctx_plan(ms_ctx* ctx, unsigned V, unsigned log_n, bool inverse, uint64_t h, ms_ntt_plan** out);     // the context's cached plan

@@ -54,6 +54,8 @@ void plans_release_ctx(ms_ctx* ctx) {
 static int plan_create_impl(ms_ctx* ctx, int field, unsigned log_n, int inverse, const void* h_offset, const void* h_group_gen, ms_ntt_plan** out) {
     unsigned V = 0;
     MSCHK(field_words(field, &V));
+    MSCHK(canon_host(ctx, "ms_ntt_plan_create", "h_offset", V == 4 ? MS_STARK252_FP : MS_GOLDILOCKS_FP, h_offset, 1));      // twiddles are in Fp = F::FftField
+    MSCHK(canon_host(ctx, "ms_ntt_plan_create", "h_group_gen", V == 4 ? MS_STARK252_FP : MS_GOLDILOCKS_FP, h_group_gen, 1));
     if (V == 4) {
         // the 252-bit plans are cached per context like the Goldilocks ones (round 5: a handle used to build its own tables -- 2^18 powers
         // of a 252-bit root on the host, 6-16 ms per `GpuFft::from(domain)` in the reference's criterion harness, gpu/benches/fft.rs)
@@ -1011,18 +1013,25 @@ extern "C" int ms_ntt_encode(ms_ntt_plan* plan, void* d_column) {
     plan->queue.push_back(d_column);
     return MS_OK;
 }
+// checked mode: the columns of a transform are scanned no later than the launch that would read them -- ms_ntt_encode only queues a pointer,
+// ms_ntt_execute checks the queue (as d_column, the name it was handed in under)
+static int ntt_enqueue(ms_ntt_plan* plan, void* const* d_columns, unsigned ncols, const char* entry, const char* arg) {
+    MSCHK(canon_cols(plan->ctx, entry, arg, field_of_words(plan->V), (size_t)1 << plan->log_n, (const void* const*)d_columns, ncols));
+    std::lock_guard<std::mutex> lk(plan->ctx->mu);
+    return plan_run(plan, (const void* const*)d_columns, d_columns, ncols, 256);
+}
 extern "C" int ms_ntt_enqueue(ms_ntt_plan* plan, void* const* d_columns, unsigned ncols) {
     if (!plan || (!d_columns && ncols)) return fail(MS_ERR_INVALID, "ms_ntt_enqueue: null argument");
     if (!user_plan_alive(plan)) return fail(MS_ERR_INVALID, "ms_ntt_enqueue: the plan's context has been destroyed");
     if (ncols == 0) return MS_OK;
-    std::lock_guard<std::mutex> lk(plan->ctx->mu);
-    return plan_run(plan, (const void* const*)d_columns, d_columns, ncols, 256);
+    return ntt_enqueue(plan, d_columns, ncols, "ms_ntt_enqueue", "d_columns");
 }
 extern "C" int ms_ntt_enqueue_to(ms_ntt_plan* plan, const void* const* d_src, void* const* d_dst, unsigned ncols) {
     if (!plan || ((!d_src || !d_dst) && ncols)) return fail(MS_ERR_INVALID, "ms_ntt_enqueue_to: null argument");
     if (!user_plan_alive(plan)) return fail(MS_ERR_INVALID, "ms_ntt_enqueue_to: the plan's context has been destroyed");
     for (unsigned c = 0; c < ncols; c++) if (!d_src[c] || !d_dst[c]) return fail(MS_ERR_INVALID, "ms_ntt_enqueue_to: null column %u", c);
     if (ncols == 0) return MS_OK;
+    MSCHK(canon_cols(plan->ctx, "ms_ntt_enqueue_to", "d_src", field_of_words(plan->V), (size_t)1 << plan->log_n, d_src, ncols));
     std::lock_guard<std::mutex> lk(plan->ctx->mu);
     return plan_run(plan, d_src, d_dst, ncols, 256);
 }
@@ -1031,7 +1040,7 @@ extern "C" int ms_ntt_execute(ms_ntt_plan* plan) {
     if (!user_plan_alive(plan)) return fail(MS_ERR_INVALID, "ms_ntt_execute: the plan's context has been destroyed");
     std::vector<void*> q;
     { std::lock_guard<std::mutex> lk(plan->ctx->mu); q.swap(plan->queue); }
-    if (!q.empty()) MSCHK(ms_ntt_enqueue(plan, q.data(), (unsigned)q.size()));
+    if (!q.empty()) MSCHK(ntt_enqueue(plan, q.data(), (unsigned)q.size(), "ms_ntt_execute", "d_column"));
     HIPCHK(hipStreamSynchronize(plan->ctx->stream));
     return MS_OK;
 }
@@ -1096,6 +1105,9 @@ extern "C" int ms_lde(ms_ctx* ctx, int field, unsigned log_n, unsigned log_blowu
     unsigned V = 0;
     MSCHK(field_words(field, &V));
     const unsigned log_N = log_n + log_blowup;
+    if (log_N > 40 || (V != 4 && log_N > 32)) return fail(MS_ERR_INVALID, V == 4 ? "LDE domain 2^%u too large" : "LDE domain 2^%u exceeds the two-adicity", log_N);
+    MSCHK(canon_host(ctx, "ms_lde", "h_offset", V == 4 ? MS_STARK252_FP : MS_GOLDILOCKS_FP, h_offset, 1));
+    MSCHK(canon_cols(ctx, "ms_lde", "d_in", field, (size_t)1 << log_n, d_in, ncols));
     if (V == 4) {
         // compute-bound field: iNTT into the head of the output column, explicit zero padding, coset NTT,
         // bit reversal -- the plain sequence (the fused / pruned passes are Goldilocks kernels)
@@ -1165,6 +1177,9 @@ extern "C" int ms_evaluate(ms_ctx* ctx, int field, unsigned log_n, unsigned log_
     if (log_n > log_domain) return fail(MS_ERR_INVALID, "more coefficients (2^%u) than domain points (2^%u)", log_n, log_domain);
     const unsigned log_blowup = log_domain - log_n;
     const size_t n = (size_t)1 << log_n, N = (size_t)1 << log_domain;
+    if (log_domain > 40 || (V != 4 && log_domain > 32)) return fail(MS_ERR_INVALID, V == 4 ? "domain 2^%u too large" : "domain 2^%u exceeds the two-adicity", log_domain);
+    MSCHK(canon_host(ctx, "ms_evaluate", "h_offset", V == 4 ? MS_STARK252_FP : MS_GOLDILOCKS_FP, h_offset, 1));
+    MSCHK(canon_cols(ctx, "ms_evaluate", "d_in", field, n, d_in, ncols));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     ms_ntt_plan* fwd = nullptr;

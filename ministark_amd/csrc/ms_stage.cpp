@@ -45,6 +45,8 @@ extern "C" int ms_binary(ms_ctx* ctx, int op, int lf, int rf, size_t n, void* d_
     if (n == 0) return MS_OK;
     const size_t sh = norm_shift(shift, n);
     MSCHK(binary_overlap("ms_binary", n, VL, VR, sh, d_dst, d_lhs, d_rhs));
+    MSCHK(canon_col(ctx, "ms_binary", "d_lhs", lf, n, d_lhs));
+    MSCHK(canon_col(ctx, "ms_binary", "d_rhs", rf, n, d_rhs));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     uint64_t* dst = (uint64_t*)d_dst; const uint64_t* l = (const uint64_t*)d_lhs; const uint64_t* r = (const uint64_t*)d_rhs;
@@ -69,6 +71,8 @@ extern "C" int ms_binary_const(ms_ctx* ctx, int op, int lf, int rf, size_t n, vo
     MSCHK(field_pair(lf, rf, &VL, &VR));
     if (n == 0) return MS_OK;
     MSCHK(disjoint_or_same("ms_binary_const", "d_lhs", d_dst, n * VL * 8, d_lhs, n * VL * 8));
+    MSCHK(canon_host(ctx, "ms_binary_const", "h_const", rf, h_const, 1));
+    MSCHK(canon_col(ctx, "ms_binary_const", "d_lhs", lf, n, d_lhs));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     msstage::Const3 c = {{0, 0, 0, 0}};
@@ -95,6 +99,8 @@ extern "C" int ms_mul_pow(ms_ctx* ctx, int lf, int rf, size_t n, void* d_dst, co
     if (n == 0) return MS_OK;
     const size_t sh = norm_shift(shift, n);
     MSCHK(binary_overlap("ms_mul_pow", n, VL, VR, sh, d_dst, d_lhs, d_rhs));
+    MSCHK(canon_col(ctx, "ms_mul_pow", "d_lhs", lf, n, d_lhs));
+    MSCHK(canon_col(ctx, "ms_mul_pow", "d_rhs", rf, n, d_rhs));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     uint64_t* dst = (uint64_t*)d_dst; const uint64_t* l = (const uint64_t*)d_lhs; const uint64_t* r = (const uint64_t*)d_rhs;
@@ -115,6 +121,7 @@ extern "C" int ms_unary(ms_ctx* ctx, int op, int field, size_t n, void* d_dst, c
     MSCHK(field_words(field, &V));
     if (n == 0) return MS_OK;
     MSCHK(disjoint_or_same("ms_unary", "d_src", d_dst, n * V * 8, d_src, n * V * 8));
+    MSCHK(canon_col(ctx, "ms_unary", "d_src", field, n, d_src));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     uint64_t* dst = (uint64_t*)d_dst; const uint64_t* src = (const uint64_t*)d_src;
@@ -152,6 +159,7 @@ extern "C" int ms_convert(ms_ctx* ctx, int dst_field, int src_field, size_t n, v
     if (n == 0) return MS_OK;
     // equal fields: the same buffer is a no-op, disjoint ones a copy; the embedding writes 3 words per word read and has no in-place form
     MSCHK(disjoint_or_same("ms_convert", "d_src", d_dst, n * VD * 8, d_src, n * VS * 8, VD == VS));
+    MSCHK(canon_col(ctx, "ms_convert", "d_src", src_field, n, d_src));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     if (VD == VS) {
@@ -169,6 +177,7 @@ extern "C" int ms_fill(ms_ctx* ctx, int field, size_t n, void* d_dst, const void
     unsigned V = 0;
     MSCHK(field_words(field, &V));
     if (n == 0) return MS_OK;
+    MSCHK(canon_host(ctx, "ms_fill", "h_value", field, h_value, 1));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     msstage::Const3 c = {{0, 0, 0, 0}};
@@ -189,6 +198,7 @@ extern "C" int ms_sum_columns(ms_ctx* ctx, int field, size_t n, const void* cons
         if (!d_cols[c]) return fail(MS_ERR_INVALID, "ms_sum_columns: null column %u", c);
         MSCHK(disjoint_or_same("ms_sum_columns", "a column", d_dst, n * V * 8, d_cols[c], n * V * 8));
     }
+    MSCHK(canon_cols(ctx, "ms_sum_columns", "d_cols", field, n, d_cols, ncols));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     msstage::SumParams P;
@@ -245,6 +255,12 @@ static int fri_fold_impl(ms_ctx* ctx, int field, unsigned log_n, unsigned foldin
         const size_t in_bytes = nchunks * folding_factor * V * 8, out_bytes = in_bytes / folding_factor;
         const char *a = (const char*)d_evals, *b = (const char*)d_out;
         if (a < b + out_bytes && b < a + in_bytes) return fail(MS_ERR_INVALID, "ms_fri_fold: d_out overlaps d_evals (the fold is not an in-place operation)");
+    }
+    {
+        const char* entry = whole ? "ms_fri_fold" : "ms_fri_fold_rows";
+        MSCHK(canon_host(ctx, entry, "h_alpha", field, h_alpha, 1));
+        MSCHK(canon_host(ctx, entry, "h_offset", V == 4 ? MS_STARK252_FP : MS_GOLDILOCKS_FP, h_offset, 1));
+        MSCHK(canon_col(ctx, entry, "d_evals", field, nchunks * folding_factor, d_evals));
     }
     if (V == 4) {
         f252::E h252 = f252::one();
@@ -334,6 +350,9 @@ extern "C" int ms_scan_affine(ms_ctx* ctx, int field, size_t n, const void* d_a,
     if (n == 0) return MS_OK;
     const size_t tile = (size_t)msscan::NT * scan_rows_per_lane(n, V);
     if ((n + tile - 1) / tile > 0xFFFFFFFFull) return fail(MS_ERR_UNSUPPORTED, "column too long");
+    MSCHK(canon_host(ctx, "ms_scan_affine", "h_init", field, h_init, 1));
+    MSCHK(canon_col(ctx, "ms_scan_affine", "d_a", field, n, d_a));
+    MSCHK(canon_col(ctx, "ms_scan_affine", "d_b", field, n, d_b));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     msscan::ScanParams P;

@@ -137,6 +137,8 @@ extern "C" int ms_validate_constraints(ms_ctx* ctx, int base_field, const uint32
                                        const void* const* d_periodic, const unsigned* periodic_len, unsigned nperiodic,
                                        unsigned nconstraints, uint64_t* h_first_row, uint64_t* h_rows_failed) {
     if (!ctx) return fail(MS_ERR_INVALID, "ms_validate_constraints: null argument");
+    MSCHK(canon_program(ctx, "ms_validate_constraints", base_field == MS_STARK252_FP, h_prog, ninstr, h_consts, nconst_words, log_n, nullptr, nullptr,
+                        d_base_cols, nbase, d_ext_cols, next, d_periodic, periodic_len, nperiodic));
     std::lock_guard<std::mutex> lk(ctx->mu);
     return validate_locked(ctx, base_field, h_prog, ninstr, h_consts, nconst_words, log_n, d_base_cols, nbase, d_ext_cols, next,
                            d_periodic, periodic_len, nperiodic, nconstraints, h_first_row, h_rows_failed);

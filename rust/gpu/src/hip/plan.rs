@@ -21,6 +21,15 @@ impl Planner {
         Self { ctx }
     }
     pub fn ctx(&self) -> *mut sys::ms_ctx { self.ctx }
+    /// Checked mode (include/ministark_hip.h): every entry point that does arithmetic on field data first scans its inputs for residues that
+    /// are not canonical and refuses (here: panics, with argument, column and row in the message) before anything is enqueued.  ark-ff types
+    /// cannot hold such a residue; a trace built through raw words can.  Checked calls block: a diagnostic mode.
+    pub fn set_checked(&self, on: bool) { sys::check(unsafe { sys::ms_ctx_set_checked(self.ctx, on as core::ffi::c_int) }) }
+    pub fn checked(&self) -> bool {
+        let mut on: core::ffi::c_int = 0;
+        sys::check(unsafe { sys::ms_ctx_get_checked(self.ctx, &mut on) });
+        on != 0
+    }
     /// `command_buffer.commit(); command_buffer.wait_until_completed()`
     pub fn sync(&self) { sys::check(unsafe { sys::ms_sync(self.ctx) }) }
     /// Specialised constraint kernels of this context: compiled / loaded from the on-disk cache / left to the interpreter.  The Metal arm has

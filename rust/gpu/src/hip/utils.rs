@@ -110,3 +110,21 @@ pub fn bit_reverse_device<F: GpuField>(columns: &mut [&mut DeviceVec<F>]) {
     let ptrs: Vec<*mut c_void> = columns.iter().map(|c| c.device_ptr()).collect();
     sys::check(unsafe { sys::ms_bit_reverse(get_planner().ctx(), field_id::<F>(), n.trailing_zeros(), ptrs.as_ptr(), ptrs.len() as u32) });
 }
+
+/// `ms_check_canonical` over equally long device columns: how many elements are not canonical (>= p) and where the first one is (smallest
+/// column, then smallest row; `first_word` = the component within an Fq3 element).  Blocks; writes nothing.
+pub fn check_canonical<F: GpuField>(columns: &[&DeviceVec<F>]) -> sys::ms_canon_report {
+    let mut report = sys::ms_canon_report::default();
+    let n = columns.first().map_or(0, |c| c.len());
+    assert!(columns.iter().all(|c| c.len() == n), "all columns of a scan must have the same length");
+    let ptrs: Vec<*const c_void> = columns.iter().map(|c| c.device_ptr() as *const c_void).collect();
+    sys::check(unsafe { sys::ms_check_canonical(get_planner().ctx(), field_id::<F>(), n, ptrs.as_ptr(), ptrs.len() as u32, &mut report as *mut sys::ms_canon_report as *mut c_void) });
+    report
+}
+
+/// The same rule over host values (`ms_check_canonical_host`): the index of the first non-canonical element, if any.
+pub fn first_non_canonical<F: GpuField>(values: &[F]) -> Option<usize> {
+    let mut first = 0usize;
+    sys::check(unsafe { sys::ms_check_canonical_host(field_id::<F>(), values.as_ptr() as *const c_void, values.len(), &mut first) });
+    if first < values.len() { Some(first) } else { None }
+}
