@@ -98,7 +98,9 @@ int ms_profile_read(ms_ctx* ctx, char* buf, size_t cap);
  *                 ms_unary, ms_convert, ms_fill, ms_sum_columns, ms_sha256_rows[_row_major], ms_blake2s_rows[_row_major],
  *                 ms_rpo256_rows[_row_major | _field], ms_rpo256_merkle (its leaves are Fp elements), ms_eval_program[_ex],
  *                 ms_validate_constraints (columns, d_x_lde, h_domain_offset, the constant words), ms_scan_affine, ms_fri_fold[_rows],
- *                 ms_horner_eval, ms_deep_rows, ms_deep_compose (columns, points, alphas, OOD values, the degree pair, h_offset).
+ *                 ms_horner_eval, ms_deep_rows, ms_deep_compose (columns, points, alphas, OOD values, the degree pair, h_offset); of
+ *                 ministark_hip_transcript.h: ms_fri_fold_dev (the one element at d_alpha as well) and ms_coin_reseed_elements[_host]
+ *                 (what the coin DRAWS is canonical by construction).
  *   NOT checked:  entry points that only move words -- ms_copy, ms_upload, ms_download, ms_bit_reverse, ms_deinterleave, ms_gather_rows,
  *                 ms_gather_digests[_multi], the byte-digest merkle builders (ms_sha256_merkle, ms_blake2s_merkle), the proof-of-work
  *                 grinders and the RCCL exchange. */

@@ -42,6 +42,12 @@ class CanonReport(ctypes.Structure):
         return f"CanonReport(count={self.count}, first_col={self.first_col}, first_row={self.first_row}, first_word={self.first_word})"
 
 
+class CoinState(ctypes.Structure):
+    """`ms_coin_state` of include/ministark_hip_transcript.h: the public coin's seed, counter and unread bytes."""
+    _fields_ = [("seed", ctypes.c_uint8 * 32), ("counter", ctypes.c_uint64), ("nbytes", ctypes.c_uint32), ("pad", ctypes.c_uint32),
+                ("bytes", ctypes.c_uint8 * 32)]
+
+
 class Lib:
     """Typed view of the C ABI in include/ministark_hip.h."""
 
@@ -126,12 +132,28 @@ class Lib:
             "ms_p2p_batch": (i, [vp, vp, sz]),
             "ms_sha256_rows_row_major": (i, [vp, i, sz, u, vp, vp]),
         }
+        # include/ministark_hip_transcript.h: the device-resident public coin and the fold that reads its challenge on the device
+        transcript_sigs = {
+            "ms_fri_fold_dev": (i, [vp, i, u, u, vp, vp, vp, vp]),
+            "ms_coin_create": (i, [vp, i, vp, c_void_pp]),
+            "ms_coin_destroy": (i, [vp, vp]),
+            "ms_coin_read": (i, [vp, vp, vp]),
+            "ms_coin_write": (i, [vp, vp, vp]),
+            "ms_coin_reseed_digest": (i, [vp, vp, vp]),
+            "ms_coin_reseed_int": (i, [vp, vp, ctypes.c_uint64]),
+            "ms_coin_reseed_elements": (i, [vp, vp, i, vp, sz]),
+            "ms_coin_reseed_elements_host": (i, [vp, vp, i, vp, sz]),
+            "ms_coin_draw": (i, [vp, vp, i, sz, vp]),
+            "ms_coin_draw_queries": (i, [vp, vp, sz, sz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(sz)]),
+            "ms_coin_pow_grind": (i, [vp, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        }
         self.optional = {}
-        for name, (res, args) in sigs.items():
+        for name, (res, args) in list(sigs.items()) + list(transcript_sigs.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
         self.sigs = sigs
+        self.transcript_sigs = transcript_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

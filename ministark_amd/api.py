@@ -426,6 +426,11 @@ class MerkleTree:
                     "height": n.bit_length() - 1}
         return fetch
 
+    def root_ptr(self):
+        """The device address of nodes[1], the root: what `PublicCoin.reseed_digest` absorbs without a download (every hash: an RPO-256
+        root is its 4 Fp elements as they lie in memory)."""
+        return self.nodes.ptr + 32
+
     def root(self):
         out = np.empty(32, dtype=np.uint8)
         self.planner.lib.check(self.planner.lib.ms_download(self.planner.handle, out.ctypes.data, self.nodes.ptr + 32, 32))
@@ -836,10 +841,18 @@ class Queries:
 def apply_drp(evals, alpha, folding_factor, domain_offset=1):
     """`apply_drp(evals, domain_offset, alpha, folding_factor)` (src/fri.rs:526-567): `evals`
     is a GpuVec in bit-reversed order; returns the next layer's evaluations (bit-reversed).
-    `alpha`: numpy u64 limbs (Montgomery) of one element of the column's field."""
+    `alpha`: numpy u64 limbs (Montgomery) of one element of the column's field, or a one-element GpuVec of that field -- the
+    challenge where the device-resident coin drew it (coin.PublicCoin.draw): the fold then reads it on the device (ms_fri_fold_dev)."""
     pl = evals.planner
     n = len(evals)
     out = GpuVec(pl, n // folding_factor, evals.field)
+    if isinstance(alpha, GpuVec):
+        if len(alpha) != 1 or alpha.field != evals.field:
+            raise ValueError("apply_drp: a device alpha is ONE element of the layer's field")
+        off = _offset_words(evals.field, domain_offset)
+        pl.lib.check(pl.lib.ms_fri_fold_dev(pl.handle, evals.field, n.bit_length() - 1, folding_factor, alpha.ptr,
+                                            off.ctypes.data, evals.ptr, out.ptr))
+        return out
     al = np.ascontiguousarray(alpha, dtype=np.uint64).ravel()
     assert al.size == FIELD_WORDS[evals.field]
     off = _offset_words(evals.field, domain_offset)

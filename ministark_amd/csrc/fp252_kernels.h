@@ -148,5 +148,36 @@ __global__ void __launch_bounds__(NT, 2) fri_fold252(Fold252Params P) {      // 
     for (int k = FF - 2; k >= 0; k--) acc = f252::add(f252::mul(acc, beta), A[k]);
     st(P.dst, c, acc);
 }
+// ms_fri_fold_dev: the same fold with alpha read from device memory (P.alpha is unused), as msfri::fri_fold_dev
+template <int FF>
+__global__ void __launch_bounds__(NT, 2) fri_fold252_dev(Fold252Params P, const uint64_t* __restrict__ d_alpha) {
+    constexpr int LOGF = FF == 2 ? 1 : FF == 4 ? 2 : FF == 8 ? 3 : 4;
+    const size_t c = (size_t)blockIdx.x * NT + threadIdx.x;       // chunk of the shard; its position in the layer decides x_i
+    if (c >= P.nchunks) return;
+    const size_t i = P.log_m ? (size_t)(__brevll((unsigned long long)(P.first_chunk + c)) >> (64 - P.log_m)) : 0;
+    const f252::E xinv = f252::mul(pow2l(P.tw_lo, P.tw_hi, P.lo_bits, i), f252::E{{P.hinv[0], P.hinv[1], P.hinv[2], P.hinv[3]}});
+    f252::E A[FF];
+    #pragma clang loop unroll(full)
+    for (int q = 0; q < FF; q++) A[q] = ld(P.src, c * FF + q);
+    #pragma clang loop unroll(full)
+    for (int s = 1; s <= LOGF; s++) {
+        constexpr int dummy = 0; (void)dummy;
+        const int half = 1 << (s - 1);
+        #pragma clang loop unroll(full)
+        for (int q = 0; q < FF / 2; q++) {
+            const int k = q & (half - 1), lo = ((q >> (s - 1)) << s) + k, hi = lo + half;
+            const int e = k << (LOGF - s);
+            const f252::E t = e ? f252::mul(A[hi], f252::E{{P.zinv[e][0], P.zinv[e][1], P.zinv[e][2], P.zinv[e][3]}}) : A[hi];
+            const f252::E u = A[lo];
+            A[lo] = f252::add(u, t);
+            A[hi] = f252::sub(u, t);
+        }
+    }
+    const f252::E beta = f252::mul(ld(d_alpha, 0), xinv);
+    f252::E acc = A[FF - 1];
+    #pragma clang loop unroll(full)
+    for (int k = FF - 2; k >= 0; k--) acc = f252::add(f252::mul(acc, beta), A[k]);
+    st(P.dst, c, acc);
+}
 
 }  // namespace ms252

@@ -73,4 +73,49 @@ __global__ void __launch_bounds__(NT) fri_fold(FoldParams P) {
     }
 }
 
+// ms_fri_fold_dev: fri_fold with the challenge read from device memory (P.alpha is unused) -- where the public coin drew it
+// (coin_kernels.h), so that no host round trip separates a layer's commitment from its fold.  Same arithmetic, same words.
+template <int FF, int V>
+__global__ void __launch_bounds__(NT) fri_fold_dev(FoldParams P, const uint64_t* __restrict__ d_alpha) {
+    const size_t c = (size_t)blockIdx.x * NT + threadIdx.x;
+    const unsigned log_m = P.log_m & 255, tshift = P.log_m >> 8;
+    if (c >= P.count) return;
+    uint64_t alpha[V];                                 // wave-uniform: one load per lane, before the Horner loop
+    #pragma unroll
+    for (int v = 0; v < V; v++) alpha[v] = d_alpha[v];
+    // x_i^-1 = h^-1 w_n^-i,  i = bitrev(c0 + c);  the table holds powers of w_N^-1 with N = n << tshift
+    const size_t i = log_m ? (size_t)(__brevll((unsigned long long)(P.c0 + c)) >> (64 - log_m)) : 0;
+    const size_t e = i << tshift;
+    uint64_t xinv = P.tw_lo[e & ((1u << P.lo_bits) - 1)];
+    if (e >> P.lo_bits) xinv = gld::mmul(xinv, P.tw_hi[e >> P.lo_bits]);
+    xinv = gld::mmul(xinv, P.hinv);
+    uint64_t A[V][FF];
+    const uint64_t* __restrict__ in = P.src + c * FF * V;
+    #pragma unroll
+    for (int q = 0; q < FF; q++) {
+        #pragma unroll
+        for (int v = 0; v < V; v++) A[v][q] = in[q * V + v];
+    }
+    #pragma unroll
+    for (int v = 0; v < V; v++) {
+        gld::dft_lazy<FF, true, true>(A[v]);          // inputs are stored in bit-reversed j order
+        #pragma unroll
+        for (int q = 0; q < FF; q++) A[v][q] = gld::canon(A[v][q]);
+    }
+    if constexpr (V == 1) {
+        const uint64_t beta = gld::mmul(alpha[0], xinv);
+        uint64_t acc = A[0][FF - 1];
+        #pragma unroll
+        for (int k = FF - 2; k >= 0; k--) acc = gl::add(gld::mmul(acc, beta), A[0][k]);
+        P.dst[c] = acc;
+    } else {
+        using F3 = msstage::Fq3T;
+        const gl::Fq3 beta = {gld::mmul(alpha[0], xinv), gld::mmul(alpha[1], xinv), gld::mmul(alpha[2], xinv)};
+        gl::Fq3 acc = {A[0][FF - 1], A[1][FF - 1], A[2][FF - 1]};
+        #pragma unroll
+        for (int k = FF - 2; k >= 0; k--) acc = gl::add(F3::mul(acc, beta), gl::Fq3{A[0][k], A[1][k], A[2][k]});
+        P.dst[3 * c] = acc.c0; P.dst[3 * c + 1] = acc.c1; P.dst[3 * c + 2] = acc.c2;
+    }
+}
+
 }  // namespace msfri

@@ -390,6 +390,8 @@ public:
         check(ms_download(pl_->ctx(), r.data(), (const char*)nodes_ + 32, 32));
         return r;
     }
+    // the device address of nodes[1]: what PublicCoin::reseed_digest absorbs without a download (an RPO-256 root as its 32 bytes lie)
+    const void* root_ptr() const { return (const char*)nodes_ + 32; }
     ~MerkleTree() { if (leaves_) ms_free(pl_->ctx(), leaves_); if (nodes_) ms_free(pl_->ctx(), nodes_); }
     MerkleTree(MerkleTree&& o) noexcept : pl_(o.pl_), n_(o.n_), leaves_(o.leaves_), nodes_(o.nodes_) { o.leaves_ = o.nodes_ = nullptr; }
 private:

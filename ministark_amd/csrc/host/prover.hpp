@@ -4,10 +4,12 @@
 //   scan_affine / running_product     examples/brainfuck/trace.rs:108-289 (extension-column loops)
 //   Queries                           src/trace.rs:113-157
 //   grind_proof_of_work               src/random.rs:48-55
+//   PublicCoin                        src/random.rs:61-141, as ProverChannel uses it (src/channel.rs:46-100); state on the device
 //   GpuRpo256ColumnMajor / RowMajor / gen_rpo_merkle_tree   gpu/src/plan.rs:32-174
 // Host values of Fq are canonical integers: FqVal{c0,c1,c2} (c1 = c2 = 0 when Fq = Fp).
 #pragma once
 #include "ministark.hpp"
+#include "../../../include/ministark_hip_transcript.h"
 #include <stdint.h>
 // host arithmetic of the 252-bit field (points and offsets of its composer): the library's own fp252.h, kept inside ms:: so that its
 // Goldilocks namespace does not meet ms::gl in a program that says `using namespace ms`
@@ -52,6 +54,17 @@ inline GpuVec<F> apply_drp(const GpuVec<F>& evals, const std::vector<uint64_t>& 
     unsigned log_n = 0; while (((size_t)1 << log_n) < evals.len()) log_n++;
     const auto off = offset_words<F>(domain_offset);
     check(ms_fri_fold(evals.planner().ctx(), F::id, log_n, folding_factor, alpha.data(), off.data(), evals.ptr(), out.ptr()));
+    return out;
+}
+// the same fold with the challenge where the device-resident coin drew it (PublicCoin::draw): one element of F in device memory,
+// read by the kernel (ms_fri_fold_dev) -- no host wait between a layer's commitment and its fold
+template <class F>
+inline GpuVec<F> apply_drp(const GpuVec<F>& evals, const GpuVec<F>& alpha, unsigned folding_factor, uint64_t domain_offset = 1) {
+    if (alpha.len() != 1) throw std::invalid_argument("apply_drp: a device alpha is one element");
+    GpuVec<F> out(evals.planner(), evals.len() / folding_factor);
+    unsigned log_n = 0; while (((size_t)1 << log_n) < evals.len()) log_n++;
+    const auto off = offset_words<F>(domain_offset);
+    check(ms_fri_fold_dev(evals.planner().ctx(), F::id, log_n, folding_factor, alpha.ptr(), off.data(), evals.ptr(), out.ptr()));
     return out;
 }
 // the same fold on a row shard of a layer of 2^log_n evaluations: `shard` holds chunks [first_chunk, first_chunk + shard.len() / folding_factor)
@@ -161,6 +174,36 @@ inline uint64_t grind_proof_of_work(Planner& pl, const std::array<uint8_t, 32>& 
     else check(ms_sha256_pow_grind(pl.ctx(), seed.data(), proof_of_work_bits, max_nonce, &nonce));
     return nonce;
 }
+
+// PublicCoinImpl<F, H> (src/random.rs:61-141) with its state in device memory (ms_coin_*): H = SHA-256, or BLAKE2s-256 for Hash::Blake2s.
+// The reseeds and draw() enqueue and return; draw_queries, grind and state wait for the device.
+class PublicCoin {
+public:
+    PublicCoin(Planner& pl, const std::array<uint8_t, 32>& seed, Hash h = Hash::Sha256) : pl_(&pl) {                // PublicCoin::new
+        check(ms_coin_create(pl.ctx(), h == Hash::Blake2s ? MS_HASH_BLAKE2S : MS_HASH_SHA256, seed.data(), &coin_));
+    }
+    ~PublicCoin() { if (coin_) ms_coin_destroy(pl_->ctx(), coin_); }
+    PublicCoin(const PublicCoin&) = delete; PublicCoin& operator=(const PublicCoin&) = delete;
+    void reseed_digest(const void* d_digest32) { check(ms_coin_reseed_digest(pl_->ctx(), coin_, d_digest32)); }  // e.g. tree.root_ptr()
+    void reseed_int(uint64_t value) { check(ms_coin_reseed_int(pl_->ctx(), coin_, value)); }
+    template <class F> void reseed_elements(const GpuVec<F>& elems, size_t count) { check(ms_coin_reseed_elements(pl_->ctx(), coin_, F::id, elems.ptr(), count)); }
+    template <class F> void reseed_elements(const GpuVec<F>& elems) { reseed_elements(elems, elems.len()); }
+    template <class F> void reseed_elements(const std::vector<uint64_t>& mont_words) {                            // host elements, Montgomery words
+        check(ms_coin_reseed_elements_host(pl_->ctx(), coin_, F::id, mont_words.data(), mont_words.size() / F::words));
+    }
+    template <class F> GpuVec<F> draw(size_t count = 1) { GpuVec<F> out(*pl_, count); check(ms_coin_draw(pl_->ctx(), coin_, F::id, count, out.ptr())); return out; }
+    std::vector<size_t> draw_queries(size_t max_n, size_t domain_size) {
+        std::vector<uint64_t> pos(max_n ? max_n : 1);
+        size_t n = 0;
+        check(ms_coin_draw_queries(pl_->ctx(), coin_, max_n, domain_size, pos.data(), &n));
+        return std::vector<size_t>(pos.begin(), pos.begin() + n);
+    }
+    uint64_t grind(unsigned bits, uint64_t max_nonce = (uint64_t)1 << 40) { uint64_t nonce = 0; check(ms_coin_pow_grind(pl_->ctx(), coin_, bits, max_nonce, &nonce)); return nonce; }
+    ms_coin_state state() const { ms_coin_state st; check(ms_coin_read(pl_->ctx(), coin_, &st)); return st; }
+private:
+    Planner* pl_;
+    void* coin_ = nullptr;
+};
 
 // DeepPolyComposer::new(air, z, base_trace_polys, extension_trace_polys, composition_trace_polys)
 // trace_arguments: the AIR's (column, offset) pairs (air.trace_arguments()).  Polynomials are coefficient-form

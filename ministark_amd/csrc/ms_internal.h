@@ -1,5 +1,5 @@
 // Internal declarations shared by the translation units of libministark_hip.so (ms_core / ms_ntt / ms_hash / ms_stage /
-// ms_eval / ms_deep / ms_comm .cpp): the context, the plan object, error plumbing, pooled scratch.  Not part of the C ABI.
+// ms_eval / ms_deep / ms_comm / ms_coin .cpp): the context, the plan object, error plumbing, pooled scratch.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/ministark_hip.h"
+#include "../../include/ministark_hip_transcript.h"
 #include "gl.h"
 #include "fp252.h"
 #include "ntt_kernels.h"
@@ -66,6 +67,7 @@ struct ms_ctx {
     std::multimap<size_t, void*> pool;
     size_t pool_bytes = 0, pool_cap = (size_t)96 << 30;
     std::map<void*, size_t> live;            // size of every block handed out by ms_alloc
+    std::map<void*, int> coins;              // public coins created on this context (ms_coin.cpp): device state -> MS_HASH_*
     // pinned staging ring for the small host arrays entry points take (query positions, digest indices): the copy to the
     // device is then truly asynchronous and the call does not drain the stream (stage_upload)
     char* stage = nullptr;

@@ -224,22 +224,38 @@ static void launch_fold(unsigned ff, dim3 g, hipStream_t st, const msfri::FoldPa
     default: hipLaunchKernelGGL((msfri::fri_fold<16, V>), g, dim3(msfri::NT), 0, st, P); break;
     }
 }
-static int fri_fold_impl(ms_ctx* ctx, int field, unsigned log_n, unsigned folding_factor, const void* h_alpha,
+template <int V>
+static void launch_fold_dev(unsigned ff, dim3 g, hipStream_t st, const msfri::FoldParams& P, const uint64_t* d_alpha) {
+    switch (ff) {
+    case 2: hipLaunchKernelGGL((msfri::fri_fold_dev<2, V>), g, dim3(msfri::NT), 0, st, P, d_alpha); break;
+    case 4: hipLaunchKernelGGL((msfri::fri_fold_dev<4, V>), g, dim3(msfri::NT), 0, st, P, d_alpha); break;
+    case 8: hipLaunchKernelGGL((msfri::fri_fold_dev<8, V>), g, dim3(msfri::NT), 0, st, P, d_alpha); break;
+    default: hipLaunchKernelGGL((msfri::fri_fold_dev<16, V>), g, dim3(msfri::NT), 0, st, P, d_alpha); break;
+    }
+}
+static int fri_fold_impl(ms_ctx* ctx, const char* entry, int field, unsigned log_n, unsigned folding_factor, const void* h_alpha, const void* d_alpha,
                          const void* h_offset, size_t first_chunk, size_t nchunks, bool whole, const void* d_evals, void* d_out);
 extern "C" int ms_fri_fold(ms_ctx* ctx, int field, unsigned log_n, unsigned folding_factor, const void* h_alpha,
                            const void* h_offset, const void* d_evals, void* d_out) {
-    return fri_fold_impl(ctx, field, log_n, folding_factor, h_alpha, h_offset, 0, 0, true, d_evals, d_out);
+    return fri_fold_impl(ctx, "ms_fri_fold", field, log_n, folding_factor, h_alpha, nullptr, h_offset, 0, 0, true, d_evals, d_out);
 }
 // A row shard of a layer: chunks [first_chunk, first_chunk + nchunks) of the bit-reversed layer of 2^log_n evaluations (d_evals holds
 // those nchunks * folding_factor evaluations, d_out receives nchunks).  The fold of a chunk needs nothing but the chunk and its
 // position, so a rank that holds rows [r n / G, (r + 1) n / G) of a layer produces its rows of the next one without communication.
 extern "C" int ms_fri_fold_rows(ms_ctx* ctx, int field, unsigned log_n, unsigned folding_factor, const void* h_alpha,
                                 const void* h_offset, size_t first_chunk, size_t nchunks, const void* d_evals, void* d_out) {
-    return fri_fold_impl(ctx, field, log_n, folding_factor, h_alpha, h_offset, first_chunk, nchunks, false, d_evals, d_out);
+    return fri_fold_impl(ctx, "ms_fri_fold_rows", field, log_n, folding_factor, h_alpha, nullptr, h_offset, first_chunk, nchunks, false, d_evals, d_out);
 }
-static int fri_fold_impl(ms_ctx* ctx, int field, unsigned log_n, unsigned folding_factor, const void* h_alpha,
+// The challenge in device memory (exactly one of h_alpha / d_alpha is given to fri_fold_impl): the kernel reads it when it runs, so the
+// fold can be enqueued behind the launch that draws it (ms_coin_draw).
+extern "C" int ms_fri_fold_dev(ms_ctx* ctx, int field, unsigned log_n, unsigned folding_factor, const void* d_alpha,
+                               const void* h_offset, const void* d_evals, void* d_out) {
+    if (!d_alpha) return fail(MS_ERR_INVALID, "ms_fri_fold_dev: null argument");
+    return fri_fold_impl(ctx, "ms_fri_fold_dev", field, log_n, folding_factor, nullptr, d_alpha, h_offset, 0, 0, true, d_evals, d_out);
+}
+static int fri_fold_impl(ms_ctx* ctx, const char* entry, int field, unsigned log_n, unsigned folding_factor, const void* h_alpha, const void* d_alpha,
                          const void* h_offset, size_t first_chunk, size_t nchunks, bool whole, const void* d_evals, void* d_out) {
-    if (!ctx || !h_alpha || !d_evals || !d_out) return fail(MS_ERR_INVALID, "ms_fri_fold: null argument");
+    if (!ctx || (!h_alpha && !d_alpha) || !d_evals || !d_out) return fail(MS_ERR_INVALID, "ms_fri_fold: null argument");
     unsigned V = 0;
     MSCHK(field_words(field, &V));
     if (folding_factor != 2 && folding_factor != 4 && folding_factor != 8 && folding_factor != 16)
@@ -255,10 +271,12 @@ static int fri_fold_impl(ms_ctx* ctx, int field, unsigned log_n, unsigned foldin
         const size_t in_bytes = nchunks * folding_factor * V * 8, out_bytes = in_bytes / folding_factor;
         const char *a = (const char*)d_evals, *b = (const char*)d_out;
         if (a < b + out_bytes && b < a + in_bytes) return fail(MS_ERR_INVALID, "ms_fri_fold: d_out overlaps d_evals (the fold is not an in-place operation)");
+        if (d_alpha && ((uintptr_t)d_alpha & 7)) return fail(MS_ERR_INVALID, "ms_fri_fold_dev: d_alpha must be 8-byte aligned");
+        if (d_alpha && ranges_overlap(d_alpha, V * 8, d_out, out_bytes)) return fail(MS_ERR_INVALID, "ms_fri_fold_dev: d_out overlaps the element at d_alpha");
     }
     {
-        const char* entry = whole ? "ms_fri_fold" : "ms_fri_fold_rows";
-        MSCHK(canon_host(ctx, entry, "h_alpha", field, h_alpha, 1));
+        if (h_alpha) MSCHK(canon_host(ctx, entry, "h_alpha", field, h_alpha, 1));
+        else MSCHK(canon_col(ctx, entry, "d_alpha", field, 1, d_alpha));
         MSCHK(canon_host(ctx, entry, "h_offset", V == 4 ? MS_STARK252_FP : MS_GOLDILOCKS_FP, h_offset, 1));
         MSCHK(canon_col(ctx, entry, "d_evals", field, nchunks * folding_factor, d_evals));
     }
@@ -276,7 +294,7 @@ static int fri_fold_impl(ms_ctx* ctx, int field, unsigned log_n, unsigned foldin
         P.tw_lo = plan->d252_tw_lo; P.tw_hi = plan->d252_tw_hi; P.lo_bits = plan->lo_bits; P.log_m = log_n - log_ff;
         const f252::E hinv = f252::inv(h252);
         memcpy(P.hinv, hinv.l, 32);
-        memcpy(P.alpha, h_alpha, 32);
+        if (h_alpha) memcpy(P.alpha, h_alpha, 32);
         const f252::E zinv = f252::pow_u64(f252::inv(f252::root_of_unity(log_n)), (uint64_t)1 << (log_n - log_ff));
         f252::E zp = f252::one();
         for (unsigned k = 0; k < folding_factor / 2; k++) { memcpy(P.zinv[k], zp.l, 32); zp = f252::mul(zp, zinv); }
@@ -284,7 +302,14 @@ static int fri_fold_impl(ms_ctx* ctx, int field, unsigned log_n, unsigned foldin
         const size_t m = nchunks;
         dim3 g((unsigned)((m + ms252::NT - 1) / ms252::NT));
         ProfScope ps(ctx, "fri_fold252", 32.0 * (m * folding_factor + m));
-        switch (folding_factor) {
+        const uint64_t* da = (const uint64_t*)d_alpha;
+        if (da) switch (folding_factor) {
+        case 2: hipLaunchKernelGGL(ms252::fri_fold252_dev<2>, g, dim3(ms252::NT), 0, ctx->stream, P, da); break;
+        case 4: hipLaunchKernelGGL(ms252::fri_fold252_dev<4>, g, dim3(ms252::NT), 0, ctx->stream, P, da); break;
+        case 8: hipLaunchKernelGGL(ms252::fri_fold252_dev<8>, g, dim3(ms252::NT), 0, ctx->stream, P, da); break;
+        default: hipLaunchKernelGGL(ms252::fri_fold252_dev<16>, g, dim3(ms252::NT), 0, ctx->stream, P, da); break;
+        }
+        else switch (folding_factor) {
         case 2: hipLaunchKernelGGL(ms252::fri_fold252<2>, g, dim3(ms252::NT), 0, ctx->stream, P); break;
         case 4: hipLaunchKernelGGL(ms252::fri_fold252<4>, g, dim3(ms252::NT), 0, ctx->stream, P); break;
         case 8: hipLaunchKernelGGL(ms252::fri_fold252<8>, g, dim3(ms252::NT), 0, ctx->stream, P); break;
@@ -309,14 +334,16 @@ static int fri_fold_impl(ms_ctx* ctx, int field, unsigned log_n, unsigned foldin
     P.tw_lo = plan->d_tw_lo; P.tw_hi = plan->d_tw_hi; P.lo_bits = plan->lo_bits;
     P.log_m = log_n - log_ff;
     P.hinv = gl::to_mont(gl::inv(h));
-    memcpy(P.alpha, h_alpha, V * 8);
+    if (h_alpha) memcpy(P.alpha, h_alpha, V * 8);
     // table exponent scale: w_n = w_(2^tl)^(2^(tl-log_n)); fold it into the index below
     P.log_m |= (tl - log_n) << 8;
     P.c0 = first_chunk; P.count = nchunks;
     const size_t m = nchunks;
     dim3 g((unsigned)((m + msfri::NT - 1) / msfri::NT));
     ProfScope ps(ctx, "fri_fold", 8.0 * V * (m * folding_factor + m));
-    if (V == 1) launch_fold<1>(folding_factor, g, ctx->stream, P); else launch_fold<3>(folding_factor, g, ctx->stream, P);
+    if (d_alpha) {
+        if (V == 1) launch_fold_dev<1>(folding_factor, g, ctx->stream, P, (const uint64_t*)d_alpha); else launch_fold_dev<3>(folding_factor, g, ctx->stream, P, (const uint64_t*)d_alpha);
+    } else if (V == 1) launch_fold<1>(folding_factor, g, ctx->stream, P); else launch_fold<3>(folding_factor, g, ctx->stream, P);
     HIPCHK(hipGetLastError());
     return MS_OK;
 }

@@ -20,6 +20,7 @@ of the channel's running digest (the same SHA-256 search either way); (ii) trace
 (the data-parallel work does not depend on validity), so fri.rs:244's assertion that the remainder's high coefficients
 vanish is not made; (iii) the composition constraint is lowered to its register program once per expression object, not once per proof
 (an AIR's constraints are fixed; `_lowered`).  Proof serialisation and the channel's hashing of a few digests stay on the host in the reference too.
+`prove` (below) runs the same phases with the channel in place: every challenge comes from a device-resident public coin (coin.py).
 """
 import time
 
@@ -348,4 +349,104 @@ def prove_phases(planner, trace, comp_expr, draws, blowup=4, folding=8, max_rema
     if keep:
         out.update(base_polys=base_polys, lde=lde_t, comp_evals=kept_evals, comp_polys=comp_polys, comp_lde=comp_lde,
                    deep_poly=deep_poly, deep_lde=deep, fri_layers=layers)
+    return out
+
+
+def from_mont_words(field, words):
+    """Montgomery words of base-field elements (flat) -> their canonical integers"""
+    from .api import f252_from_mont_limbs, gl_from_mont
+    w = np.asarray(words, dtype=np.uint64).ravel()
+    if field == STARK252_FP:
+        return [f252_from_mont_limbs(w[i:i + 4]) for i in range(0, len(w), 4)]
+    return [gl_from_mont(int(x)) for x in w]
+
+
+def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, folding=8, max_remainder_coeffs=64, grinding_bits=8,
+          num_queries=32, hash="sha256", keep=False, ce_blowup=None, field=GOLDILOCKS_FP, trace_args=None):
+    """The phases of `prove_phases` with every challenge drawn from the transcript: a device-resident `coin.PublicCoin` seeded with
+    `seed32` (the digest of the public inputs, src/channel.rs:33-44) stands where `Draws` stood, in the reference's order
+    (src/prover.rs:50-173, src/channel.rs:46-100, src/fri.rs:199-247):
+        commit base trace -> draw the `nchallenges` composition coefficients        commit composition trace -> draw z
+        OOD evaluations -> reseed (execution, then composition)                     draw the DEEP coefficients (src/stark.rs:41-53)
+        per FRI layer: commit -> reseed with the root -> draw alpha -> fold         remainder coefficients -> reseed
+        grind -> reseed with the nonce                                              draw the query positions -> openings
+    The FRI commit phase is enqueued without a host wait: a layer's root is absorbed where the tree builder wrote it, alpha is drawn into
+    device memory and the fold reads it there (ms_fri_fold_dev); roots and alphas are downloaded once, after the remainder.  The draws the
+    host itself needs (composition coefficients, z, DEEP coefficients) are downloaded where they are needed, as the reference's are.
+    Fq = Fp AIRs over Goldilocks or the 252-bit field; hints: canonical integers; H of the coin: BLAKE2s for a BLAKE2s prover, else SHA-256.
+    Returns what prove_phases returns (without timings), plus the draws as canonical integers: challenges, z, deep, fri_alphas, positions."""
+    from .api import GatherBatch, GpuVec
+    from .coin import PublicCoin
+    pl = planner
+    if field not in (GOLDILOCKS_FP, STARK252_FP):
+        raise ValueError("prove: field must be GOLDILOCKS_FP or STARK252_FP")
+    if field == STARK252_FP and hash == "rpo256":
+        raise ValueError("prove: RPO-256 absorbs Goldilocks elements; the 252-bit field commits with sha256 or blake2s")
+    if trace.field != field:
+        raise ValueError("prove: the trace is not over `field`")
+    h = field_generator(field)
+    n_t = trace.num_rows()
+    n_lde = n_t * blowup
+    ce_blowup = blowup if ce_blowup is None else ce_blowup
+    assert ce_blowup <= blowup                                                 # src/air.rs:149
+    n_ce = n_t * ce_blowup
+    trace_dom, lde_dom, ce_dom = Radix2EvaluationDomain(n_t, 1, field), Radix2EvaluationDomain(n_lde, h, field), Radix2EvaluationDomain(n_ce, h, field)
+    prog = _lowered(comp_expr, trace.num_cols(), field)
+    trace_args = [(c, o) for c in range(trace.num_cols()) for o in (0, 1)] if trace_args is None else list(trace_args)
+    V = 4 if field == STARK252_FP else 1
+    coin = PublicCoin(pl, seed32, pow_hash(hash))
+    out = {}
+
+    base_polys = trace.interpolate(trace_dom)                                  # prover.rs:50
+    lde_t = base_polys.bit_reversed_evaluate(lde_dom)
+    tree_t = MerkleTree.from_matrix(lde_t, hash)
+    coin.reseed_digest(tree_t.root_ptr())                                      # channel.commit_base_trace
+    ch = coin.draw(field, nchallenges).to_numpy().reshape(-1, V)               # air.get_challenges + composition coefficients (stark.rs:27-39)
+    comp_evals = E.eval(prog, pl, ch, to_mont_words(field, hints), ce_blowup, h, n_ce, lde_t.columns, bit_reversed=True)
+    kept_evals = comp_evals.clone() if keep else None
+    comp_poly = Matrix([comp_evals]).bit_reverse_rows().into_polynomials(ce_dom).columns[0]
+    comp_polys = Matrix.from_chunks(comp_poly, ce_blowup)
+    comp_lde = comp_polys.bit_reversed_evaluate(lde_dom)
+    tree_c = MerkleTree.from_matrix(comp_lde, hash)
+    coin.reseed_digest(tree_c.root_ptr())                                      # channel.commit_composition_trace
+    z = from_mont_words(field, coin.draw(field, 1).to_numpy())[0]              # channel.get_ood_point
+    composer = DeepPolyComposer(trace_args, n_t, z, base_polys, None, comp_polys)
+    out["ood"] = composer.get_ood_evals()
+    coin.reseed_elements(to_mont_words(field, list(out["ood"][0]) + list(out["ood"][1])), field)       # channel.send_ood_evals: execution, composition
+    d = from_mont_words(field, coin.draw(field, len(trace_args) + ce_blowup + 2).to_numpy())           # stark.rs:41-53
+    deep_coeffs = DeepCompositionCoeffs(d[: len(trace_args)], d[len(trace_args): len(trace_args) + ce_blowup], (d[-2], d[-1]))
+    deep_poly = composer.into_deep_poly(deep_coeffs) if keep else None
+    deep = Matrix([composer.into_deep_evaluations(deep_coeffs, lde_t, None, comp_lde, n_lde)])
+    # fri.rs:179-231: nothing below waits for the device until the remainder is reseeded
+    cur, n, layers, fri_trees, alphas = deep.columns[0], n_lde, [], [], []
+    for _ in range(fri_num_layers(n_lde, blowup, folding, max_remainder_coeffs)):
+        tree = MerkleTree.from_fri_layer(cur, folding, hash)
+        coin.reseed_digest(tree.root_ptr())                                    # channel.commit_fri_layer (fri.rs:217-223)
+        alpha = coin.draw(field, 1)                                            # channel.draw_fri_alpha (fri.rs:225-227)
+        layers.append(cur); fri_trees.append(tree); alphas.append(alpha)
+        cur = apply_drp(cur, alpha, folding, 1)
+        n //= folding
+    rem = Matrix([cur.clone()]).bit_reverse_rows().into_polynomials(Radix2EvaluationDomain(n, 1, field)).columns[0]
+    nrem = max(n // blowup, 1)
+    coin.reseed_elements(GpuVec(pl, nrem, field, ptr=rem.ptr))                 # channel.commit_remainder (fri.rs:232-248)
+    out["base_root"], out["composition_root"] = tree_t.root(), tree_c.root()
+    out["fri_roots"], out["remainder"] = [t.root() for t in fri_trees], cur
+    out["remainder_coeffs"] = rem.to_numpy()[: nrem * V]
+    out["nonce"] = coin.grind(grinding_bits)                                   # prover.rs:160, channel.rs:76-93
+    coin.reseed_int(out["nonce"])
+    positions = coin.draw_queries(num_queries, n_lde)                          # channel.get_fri_query_positions (prover.rs:161)
+    batch = GatherBatch(pl)
+    queries = Queries(lde_t, None, comp_lde, tree_t, None, tree_c, positions, batch)                    # prover.rs:163-173
+    pos, launched = positions, []
+    for layer, tree in zip(layers, fri_trees):
+        pos = fold_positions(pos, folding)
+        launched.append((pos, fri_layer_rows_launch(layer, folding, pos, batch), tree.prove_launch(pos, batch)))
+    batch.fetch()
+    out["queries"] = queries.fetch()
+    out["fri_openings"] = [{"positions": p, "rows": rows(), "proof": proof()} for p, rows, proof in launched]
+    out.update(challenges=from_mont_words(field, ch), z=z, deep=deep_coeffs, positions=positions, trace_args=trace_args,
+               fri_alphas=[from_mont_words(field, a.to_numpy())[0] for a in alphas])
+    if keep:
+        out.update(base_polys=base_polys, lde=lde_t, comp_evals=kept_evals, comp_polys=comp_polys, comp_lde=comp_lde,
+                   deep_poly=deep_poly, deep_lde=deep, fri_layers=layers, coin=coin)
     return out

@@ -20,6 +20,7 @@
 pub mod plan;
 pub mod stage;
 pub mod sys;
+pub mod sys_transcript;
 pub mod utils;
 
 pub use plan::{evaluate_device, gen_rpo_merkle_tree, get_planner, lde_device, sha256_commit_device, GpuFft, GpuIfft, GpuRpo256ColumnMajor,

@@ -5,7 +5,9 @@ scripts/prove_once.py (the LAST proof is analysed).
     python scripts/prove_gaps.py gpurun_out/gaps
 
 Prints the proof's span, the sum of kernel durations, the idle time, and the idle time grouped by the kernel that PRECEDES each gap (a gap after
-sha256_merkle_top is a root download + the host's next launches; a gap between two FRI kernels is pure launch overhead)."""
+sha256_merkle_top is a root download + the host's next launches; a gap between two FRI kernels is pure launch overhead), and the same
+figures for the FRI commit phase alone: from the first FRI layer's leaf hash to the remainder's inverse transform.  With
+TRANSCRIPT=1 scripts/prove_once.py runs pipeline.prove, whose commit phase has no download in it: no gap there should exceed a launch."""
 import csv
 import glob
 import os
@@ -15,7 +17,7 @@ from collections import defaultdict
 
 def short(name):
     name = name.split("(")[0]
-    for p in ("mssha::", "msntt2::", "mslde2::", "msdeep::", "msfri::", "mseval::", "msscan::", "msstage::", "msntt::"):
+    for p in ("mssha::", "msntt2::", "mslde2::", "msdeep::", "msfri::", "mseval::", "msscan::", "msstage::", "msntt::", "mscoin::", "msb2s::", "ms252::"):
         name = name.replace(p, "")
     return name.split("<")[0][:40]
 
@@ -50,6 +52,18 @@ def main():
     print("largest gaps:")
     for g, a, b in sorted(big, reverse=True)[:25]:
         print(f"  {g / 1e3:7.1f} us  {a} -> {b}")
+
+
+    # the FRI commit phase: the row hash that precedes the first fold ... the first transform kernel after the last fold
+    folds = [i for i, r in enumerate(proof) if "fri_fold" in r[2]]
+    if folds:
+        first = max(i for i in range(folds[0]) if "_rows" in proof[i][2])
+        last = next((i for i in range(folds[-1] + 1, len(proof)) if "ntt" in proof[i][2]), folds[-1])
+        win = proof[first:last + 1]
+        wgaps = sorted(((max(0, b[0] - a[1]), a[2], b[2]) for a, b in zip(win, win[1:])), reverse=True)
+        wspan, wbusy = win[-1][1] - win[0][0], sum(e - s for s, e, _ in win)
+        print(f"FRI commit phase ({win[0][2]} .. {win[-1][2]}): {len(win)} kernels, span {wspan / 1e3:.1f} us, kernels {wbusy / 1e3:.1f} us, "
+              f"idle {(wspan - wbusy) / 1e3:.1f} us, largest gap {wgaps[0][0] / 1e3:.1f} us ({wgaps[0][1]} -> {wgaps[0][2]})")
 
 
 if __name__ == "__main__":

@@ -1,4 +1,5 @@
-"""A few runs of pipeline.prove_phases at configs[4]'s size (for counter collection with scripts/sq_probe.sh)."""
+"""A few runs of pipeline.prove_phases at configs[4]'s size (for counter collection with scripts/sq_probe.sh); TRANSCRIPT=1: of
+pipeline.prove, whose challenges come from the device-resident public coin (the trace scripts/prove_gaps.py reduces)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -12,5 +13,8 @@ trace = Matrix([GpuVec.from_numpy(pl, np.random.default_rng(c).integers(0, P, si
 comp, ce, nch = pipeline.fib_constraints(n_t, ncols)
 draws = pipeline.Draws(0xC5, ncols, nch, ce, 32, n_t * 4, pipeline.fri_num_layers(n_t * 4, 4, 8, 64))
 for _ in range(int(os.environ.get("REPS", "3"))):
-    pipeline.prove_phases(pl, trace, comp, draws, 4, 8, 64, 8, ce_blowup=ce)
+    if os.environ.get("TRANSCRIPT") == "1":
+        pipeline.prove(pl, trace, comp, nch, draws.hints, bytes(range(32)), 4, 8, 64, 8, 32, ce_blowup=ce)
+    else:
+        pipeline.prove_phases(pl, trace, comp, draws, 4, 8, 64, 8, ce_blowup=ce)
 pl.sync()
