@@ -147,13 +147,21 @@ class Lib:
             "ms_coin_draw_queries": (i, [vp, vp, sz, sz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(sz)]),
             "ms_coin_pow_grind": (i, [vp, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         }
+        # include/ministark_hip_keccak.h: Keccak-256 / SHA3-256 commitments and proof-of-work (`variant` after the context)
+        keccak_sigs = {
+            "ms_keccak_rows": (i, [vp, i, i, sz, c_void_pp, u, vp]),
+            "ms_keccak_rows_row_major": (i, [vp, i, i, sz, u, vp, vp]),
+            "ms_keccak_merkle": (i, [vp, i, sz, vp, vp]),
+            "ms_keccak_pow_grind": (i, [vp, i, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        }
         self.optional = {}
-        for name, (res, args) in list(sigs.items()) + list(transcript_sigs.items()):
+        for name, (res, args) in list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
         self.sigs = sigs
         self.transcript_sigs = transcript_sigs
+        self.keccak_sigs = keccak_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

@@ -286,7 +286,8 @@ def _gather_digests(planner, digests, ndigests, ids):
     return _gather_digests_launch(planner, digests, ndigests, ids)()
 
 
-HASHES = ("sha256", "rpo256", "blake2s")
+HASHES = ("sha256", "rpo256", "blake2s", "keccak256", "sha3_256")
+KECCAK_VARIANTS = {"keccak256": 0, "sha3_256": 1}          # MS_KECCAK256 / MS_SHA3_256 of include/ministark_hip_keccak.h
 
 
 def merkle_view_ids(n, indices, lib=None):
@@ -361,7 +362,9 @@ class MerkleTree:
                 (gpu/src/plan.rs:32-174, README.md:90): leaves by ms_rpo256_rows_field, nodes by
                 gen_rpo_merkle_tree.  A digest is 4 Fp elements = 32 bytes, so proofs have the same shape;
       "blake2s" BLAKE2s-256 (blake2::Blake2s256, hashlib.blake2s): the leaves hash the bytes SHA-256 hashes, a merge is one
-                compression instead of two.  Any of the three fields."""
+                compression instead of two.  Any of the three fields;
+      "keccak256" / "sha3_256"  the Keccak sponge with domain byte 0x01 (sha3::Keccak256, the EVM's KECCAK256) / 0x06
+                (hashlib.sha3_256): the same leaf bytes, a merge is one permutation.  Any of the three fields."""
 
     def __init__(self, planner, leaves, nleaves, hash="sha256"):
         if hash not in HASHES:
@@ -376,6 +379,8 @@ class MerkleTree:
             L.check(L.ms_sha256_merkle(planner.handle, nleaves, leaves.ptr, self.nodes.ptr))
         elif hash == "blake2s":
             L.check(L.ms_blake2s_merkle(planner.handle, nleaves, leaves.ptr, self.nodes.ptr))
+        elif hash in KECCAK_VARIANTS:
+            L.check(L.ms_keccak_merkle(planner.handle, KECCAK_VARIANTS[hash], nleaves, leaves.ptr, self.nodes.ptr))
         else:
             L.check(L.ms_rpo256_merkle(planner.handle, nleaves, leaves.ptr, self.nodes.ptr))
 
@@ -399,6 +404,8 @@ class MerkleTree:
             pl.lib.check(pl.lib.ms_rpo256_rows_row_major(pl.handle, nrows, words, evaluations.ptr, leaves.ptr))
         elif hash == "blake2s":
             pl.lib.check(pl.lib.ms_blake2s_rows_row_major(pl.handle, evaluations.field, nrows, folding_factor, evaluations.ptr, leaves.ptr))
+        elif hash in KECCAK_VARIANTS:
+            pl.lib.check(pl.lib.ms_keccak_rows_row_major(pl.handle, KECCAK_VARIANTS[hash], evaluations.field, nrows, folding_factor, evaluations.ptr, leaves.ptr))
         else:
             raise ValueError(f"unknown hash {hash!r} (one of {HASHES})")
         return cls(pl, leaves, nrows, hash)
@@ -755,7 +762,8 @@ class Matrix:
 
     def hash_rows(self, hash="sha256"):
         """`hash_rows::<F, H>` (src/merkle.rs:412-436, src/matrix.rs:254-280): one digest per row ->
-        DeviceBytes of num_rows x 32.  H = Sha256HashFn ("sha256"), RPO-256 ("rpo256", Goldilocks columns) or BLAKE2s-256 ("blake2s")."""
+        DeviceBytes of num_rows x 32.  H = Sha256HashFn ("sha256"), RPO-256 ("rpo256", Goldilocks columns), BLAKE2s-256 ("blake2s"),
+        Keccak-256 ("keccak256") or SHA3-256 ("sha3_256")."""
         pl = self.planner
         n = self.num_rows()
         leaves = DeviceBytes(pl, n * 32)
@@ -765,6 +773,8 @@ class Matrix:
             pl.lib.check(pl.lib.ms_rpo256_rows_field(pl.handle, self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr))
         elif hash == "blake2s":
             pl.lib.check(pl.lib.ms_blake2s_rows(pl.handle, self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr))
+        elif hash in KECCAK_VARIANTS:
+            pl.lib.check(pl.lib.ms_keccak_rows(pl.handle, KECCAK_VARIANTS[hash], self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr))
         else:
             raise ValueError(f"unknown hash {hash!r} (one of {HASHES})")
         return leaves
@@ -918,20 +928,24 @@ def gen_rpo_merkle_tree(leaves):
 
 
 def pow_hash(commitment_hash):
-    """The proof-of-work hash of a prover that commits with `commitment_hash`: BLAKE2s grinds with BLAKE2s; SHA-256 and RPO-256
-    provers grind with SHA-256, as they always have."""
-    return "blake2s" if commitment_hash == "blake2s" else "sha256"
+    """The proof-of-work hash of a prover that commits with `commitment_hash`: BLAKE2s grinds with BLAKE2s, Keccak-256 and SHA3-256
+    with themselves; SHA-256 and RPO-256 provers grind with SHA-256, as they always have."""
+    return commitment_hash if commitment_hash in ("blake2s", "keccak256", "sha3_256") else "sha256"
 
 
 def grind_proof_of_work(planner, seed, proof_of_work_bits, max_nonce=(1 << 40), hash="sha256"):
     """`PublicCoin::grind_proof_of_work(bits)` (src/random.rs:48-55): the smallest nonce >= 1 whose
-    H(seed || nonce_be) has `bits` leading zero bits.  seed: 32 bytes.  H = SHA-256 ("sha256") or BLAKE2s-256 ("blake2s")."""
+    H(seed || nonce_be) has `bits` leading zero bits.  seed: 32 bytes.  H = SHA-256 ("sha256"), BLAKE2s-256 ("blake2s"),
+    Keccak-256 ("keccak256") or SHA3-256 ("sha3_256")."""
     seed = bytes(seed)
     assert len(seed) == 32
-    if hash not in ("sha256", "blake2s"):
-        raise ValueError(f"unknown proof-of-work hash {hash!r} (sha256 or blake2s)")
+    if hash not in ("sha256", "blake2s") and hash not in KECCAK_VARIANTS:
+        raise ValueError(f"unknown proof-of-work hash {hash!r} (sha256, blake2s, keccak256 or sha3_256)")
     out = ctypes.c_uint64(0)
     buf = ctypes.create_string_buffer(seed, 32)
+    if hash in KECCAK_VARIANTS:
+        planner.lib.check(planner.lib.ms_keccak_pow_grind(planner.handle, KECCAK_VARIANTS[hash], buf, proof_of_work_bits, max_nonce, ctypes.byref(out)))
+        return out.value
     grind = planner.lib.ms_blake2s_pow_grind if hash == "blake2s" else planner.lib.ms_sha256_pow_grind
     planner.lib.check(grind(planner.handle, buf, proof_of_work_bits, max_nonce, ctypes.byref(out)))
     return out.value

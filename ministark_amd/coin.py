@@ -9,15 +9,15 @@ import numpy as np
 from . import _lib
 from .api import FIELD_WORDS, DeviceBytes, GpuVec
 
-HASH_IDS = {"sha256": 0, "blake2s": 1}
+HASH_IDS = {"sha256": 0, "blake2s": 1, "keccak256": 3, "sha3_256": 4}        # 2 is left for an RPO-256 coin
 
 
 class PublicCoin:
-    """`PublicCoin::new(seed)` (src/random.rs:102-109).  seed32: 32 bytes; hash: "sha256" (Sha256HashFn) or "blake2s"."""
+    """`PublicCoin::new(seed)` (src/random.rs:102-109).  seed32: 32 bytes; hash: "sha256" (Sha256HashFn), "blake2s", "keccak256" or "sha3_256"."""
 
     def __init__(self, planner, seed32, hash="sha256"):
         if hash not in HASH_IDS:
-            raise ValueError(f"unknown coin hash {hash!r} (sha256 or blake2s)")
+            raise ValueError(f"unknown coin hash {hash!r} (one of {sorted(HASH_IDS)})")
         seed32 = bytes(seed32)
         if len(seed32) != 32:
             raise ValueError("the coin's seed is a 32-byte digest")

@@ -1,5 +1,6 @@
 // The public coin of the Fiat-Shamir transcript, resident on the device: PublicCoinImpl<F, H> (src/random.rs:61-141) as
-// ProverChannel drives it (src/channel.rs:46-100, src/fri.rs:217-247), for H = SHA-256 and H = BLAKE2s-256.
+// ProverChannel drives it (src/channel.rs:46-100, src/fri.rs:217-247), for H = SHA-256, BLAKE2s-256, Keccak-256 and SHA3-256
+// (the template parameter H is ms_coin_create's hash id: 0, 1, 3, 4; 2 is left for an RPO-256 coin).
 //
 // State (ms_coin_state of include/ministark_hip_transcript.h, 80 bytes in HBM): a 32-byte seed, a u64 counter and up to 32 unread bytes of the
 // last digest.  The rules, one device function each:
@@ -16,7 +17,7 @@
 // These are dependent chains of a few compressions: latency-bound, no roofline.  Every kernel is ONE wave; lane 0 walks the chain
 // (the state lives in its registers between the load and the store), and in coin_reseed_elements all 64 lanes hash the per-element
 // digests of a batch in parallel before lane 0 merges them in order.  The compression functions are those of sha256_kernels.h /
-// blake2s_kernels.h.  Only the proof-of-work search (one nonce per lane, as sha256_pow_grind) is a wide launch.
+// blake2s_kernels.h / keccak_sponge.h (every message here is one Keccak block; the chains keep the permutation as a short loop).  Only the proof-of-work search (one nonce per lane, as sha256_pow_grind) is a wide launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "gl.h"
@@ -24,6 +25,7 @@
 #include "fp252.h"
 #include "sha256_kernels.h"
 #include "blake2s_kernels.h"
+#include "keccak_sponge.h"
 
 namespace mscoin {
 
@@ -59,7 +61,13 @@ __device__ __forceinline__ void hash_short(const uint32_t (&m)[16], unsigned len
         }
         #pragma unroll
         for (int q = 0; q < 8; q++) out[q] = mssha::bswap32(s.h[q]);
+    } else if constexpr (H == 3 || H == 4) {     // Keccak-256 / SHA3-256: one block, the domain byte at offset len, 0x80 in byte 135
+        mskec::Keccak s;
+        s.load_short(m, len / 8, H == 3 ? mskec::DOMAIN_KECCAK : mskec::DOMAIN_SHA3);
+        s.permute<mskec::UNROLL_CHAIN>();
+        s.digest(out);
     } else {                                     // BLAKE2s: one final block, counter = len
+        static_assert(H == 1, "hash ids: 0 SHA-256, 1 BLAKE2s-256, 3 Keccak-256, 4 SHA3-256");
         msb2s::B2s s;
         s.init();
         #pragma unroll

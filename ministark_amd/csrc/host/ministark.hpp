@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../../include/ministark_hip.h"
+#include "../../../include/ministark_hip_keccak.h"
 
 namespace ms {
 
@@ -315,8 +316,11 @@ public:
 
 // H of MatrixMerkleTreeImpl<H> (src/merkle.rs:296-361): Sha256HashFn (src/hash.rs:58-100), RPO-256 over
 // Goldilocks (gpu/src/plan.rs:32-174, README.md:90) or BLAKE2s-256 (any field; the bytes SHA-256 hashes, one compression per
-// merge).  All digests are 32 bytes, proofs have the same shape.
-enum class Hash { Sha256, Rpo256, Blake2s };
+// merge), or the Keccak sponge as Keccak-256 (the EVM's KECCAK256) / SHA3-256 (any field; the same bytes, one permutation per merge).
+// All digests are 32 bytes, proofs have the same shape.
+enum class Hash { Sha256, Rpo256, Blake2s, Keccak256, Sha3_256 };
+inline bool is_keccak(Hash h) { return h == Hash::Keccak256 || h == Hash::Sha3_256; }
+inline int keccak_variant(Hash h) { return h == Hash::Sha3_256 ? MS_SHA3_256 : MS_KECCAK256; }        // `variant` of ms_keccak_*
 
 class MerkleTree {
 public:
@@ -326,6 +330,7 @@ public:
         std::vector<const void*> in; for (auto& c : m.columns) in.push_back(c.ptr());
         if (h == Hash::Sha256) check(ms_sha256_rows(t.pl_->ctx(), F::id, t.n_, in.data(), (unsigned)in.size(), t.leaves_));
         else if (h == Hash::Blake2s) check(ms_blake2s_rows(t.pl_->ctx(), F::id, t.n_, in.data(), (unsigned)in.size(), t.leaves_));
+        else if (is_keccak(h)) check(ms_keccak_rows(t.pl_->ctx(), keccak_variant(h), F::id, t.n_, in.data(), (unsigned)in.size(), t.leaves_));
         else check(ms_rpo256_rows_field(t.pl_->ctx(), F::id, t.n_, in.data(), (unsigned)in.size(), t.leaves_));
         t.build(h);
         return t;
@@ -337,6 +342,7 @@ public:
         MerkleTree t(evaluations.planner(), evaluations.len() / folding_factor);
         if (h == Hash::Sha256) check(ms_sha256_rows_row_major(t.pl_->ctx(), F::id, t.n_, folding_factor, evaluations.ptr(), t.leaves_));
         else if (h == Hash::Blake2s) check(ms_blake2s_rows_row_major(t.pl_->ctx(), F::id, t.n_, folding_factor, evaluations.ptr(), t.leaves_));
+        else if (is_keccak(h)) check(ms_keccak_rows_row_major(t.pl_->ctx(), keccak_variant(h), F::id, t.n_, folding_factor, evaluations.ptr(), t.leaves_));
         else check(ms_rpo256_rows_row_major(t.pl_->ctx(), t.n_, folding_factor * (unsigned)(ms_field_bytes(F::id) / 8), evaluations.ptr(), t.leaves_));
         t.build(h);
         return t;
@@ -399,6 +405,7 @@ private:
     void build(Hash h) {
         if (h == Hash::Sha256) check(ms_sha256_merkle(pl_->ctx(), n_, leaves_, nodes_));
         else if (h == Hash::Blake2s) check(ms_blake2s_merkle(pl_->ctx(), n_, leaves_, nodes_));
+        else if (is_keccak(h)) check(ms_keccak_merkle(pl_->ctx(), keccak_variant(h), n_, leaves_, nodes_));
         else check(ms_rpo256_merkle(pl_->ctx(), n_, leaves_, nodes_));
     }
     Pending gather_launch(const void* digests, const std::vector<uint64_t>& ids, GatherArena* arena) const {

@@ -166,21 +166,24 @@ private:
 };
 
 // PublicCoin::grind_proof_of_work(bits): the smallest nonce >= 1 with `bits` leading zero bits of H(seed || nonce_be),
-// H = SHA-256 (Hash::Sha256, also what an RPO-256 prover grinds with) or BLAKE2s-256 (Hash::Blake2s)
+// H = SHA-256 (Hash::Sha256, also what an RPO-256 prover grinds with), BLAKE2s-256 (Hash::Blake2s), Keccak-256 or SHA3-256
 inline uint64_t grind_proof_of_work(Planner& pl, const std::array<uint8_t, 32>& seed, unsigned proof_of_work_bits, uint64_t max_nonce = (uint64_t)1 << 40,
                                     Hash h = Hash::Sha256) {
     uint64_t nonce = 0;
     if (h == Hash::Blake2s) check(ms_blake2s_pow_grind(pl.ctx(), seed.data(), proof_of_work_bits, max_nonce, &nonce));
+    else if (is_keccak(h)) check(ms_keccak_pow_grind(pl.ctx(), keccak_variant(h), seed.data(), proof_of_work_bits, max_nonce, &nonce));
     else check(ms_sha256_pow_grind(pl.ctx(), seed.data(), proof_of_work_bits, max_nonce, &nonce));
     return nonce;
 }
 
-// PublicCoinImpl<F, H> (src/random.rs:61-141) with its state in device memory (ms_coin_*): H = SHA-256, or BLAKE2s-256 for Hash::Blake2s.
+// PublicCoinImpl<F, H> (src/random.rs:61-141) with its state in device memory (ms_coin_*): H = SHA-256, or BLAKE2s-256 / Keccak-256 /
+// SHA3-256 for Hash::Blake2s / Keccak256 / Sha3_256 (ids 0, 1, 3, 4; an RPO-256 prover's coin is SHA-256, id 2 is left for an RPO-256 coin).
 // The reseeds and draw() enqueue and return; draw_queries, grind and state wait for the device.
 class PublicCoin {
 public:
     PublicCoin(Planner& pl, const std::array<uint8_t, 32>& seed, Hash h = Hash::Sha256) : pl_(&pl) {                // PublicCoin::new
-        check(ms_coin_create(pl.ctx(), h == Hash::Blake2s ? MS_HASH_BLAKE2S : MS_HASH_SHA256, seed.data(), &coin_));
+        const int id = h == Hash::Blake2s ? MS_HASH_BLAKE2S : h == Hash::Keccak256 ? MS_HASH_KECCAK256 : h == Hash::Sha3_256 ? MS_HASH_SHA3_256 : MS_HASH_SHA256;
+        check(ms_coin_create(pl.ctx(), id, seed.data(), &coin_));
     }
     ~PublicCoin() { if (coin_) ms_coin_destroy(pl_->ctx(), coin_); }
     PublicCoin(const PublicCoin&) = delete; PublicCoin& operator=(const PublicCoin&) = delete;

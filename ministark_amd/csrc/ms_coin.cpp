@@ -3,6 +3,7 @@
 // builder left it and a drawn challenge is read by the next kernel where the coin wrote it (ms_fri_fold_dev): the asynchronous entry
 // points enqueue one single-wave launch and never wait.  Kernels and the rules they implement: coin_kernels.h.
 #include "ms_internal.h"
+#include "../../include/ministark_hip_keccak.h"
 #include "coin_kernels.h"
 
 using mscoin::State;
@@ -22,6 +23,8 @@ template <int OP>
 static void launch_step(ms_ctx* ctx, int hash, void* d_coin, const void* d_digest, uint64_t arg, size_t count, void* d_out) {
     const dim3 one(1), wave(mscoin::WAVE);
     if (hash == MS_HASH_SHA256) hipLaunchKernelGGL((mscoin::coin_step<0, OP>), one, wave, 0, ctx->stream, (State*)d_coin, (const uint32_t*)d_digest, arg, count, (uint64_t*)d_out);
+    else if (hash == MS_HASH_KECCAK256) hipLaunchKernelGGL((mscoin::coin_step<3, OP>), one, wave, 0, ctx->stream, (State*)d_coin, (const uint32_t*)d_digest, arg, count, (uint64_t*)d_out);
+    else if (hash == MS_HASH_SHA3_256) hipLaunchKernelGGL((mscoin::coin_step<4, OP>), one, wave, 0, ctx->stream, (State*)d_coin, (const uint32_t*)d_digest, arg, count, (uint64_t*)d_out);
     else hipLaunchKernelGGL((mscoin::coin_step<1, OP>), one, wave, 0, ctx->stream, (State*)d_coin, (const uint32_t*)d_digest, arg, count, (uint64_t*)d_out);
 }
 
@@ -41,7 +44,7 @@ static int write_state(ms_ctx* ctx, void* d_coin, const State& S) {          // 
 
 extern "C" int ms_coin_create(ms_ctx* ctx, int hash, const void* h_seed32, void** d_coin) {
     if (!ctx || !h_seed32 || !d_coin) return fail(MS_ERR_INVALID, "ms_coin_create: null argument");
-    if (hash != MS_HASH_SHA256 && hash != MS_HASH_BLAKE2S) return fail(MS_ERR_INVALID, "ms_coin_create: unknown hash id %d", hash);
+    if (hash != MS_HASH_SHA256 && hash != MS_HASH_BLAKE2S && hash != MS_HASH_KECCAK256 && hash != MS_HASH_SHA3_256) return fail(MS_ERR_INVALID, "ms_coin_create: unknown hash id %d", hash);
     void* d = nullptr;
     MSCHK(ms_alloc(ctx, sizeof(State), &d));
     State S;
@@ -118,6 +121,8 @@ static int reseed_elements_launch(ms_ctx* ctx, int hash, unsigned V, void* d_coi
     {
         ProfScope ps(ctx, "coin_reseed_elements", 8.0 * V * count);
         if (hash == MS_HASH_SHA256) launch_elements<0>(ctx, V, d_coin, d_elems, count);
+        else if (hash == MS_HASH_KECCAK256) launch_elements<3>(ctx, V, d_coin, d_elems, count);
+        else if (hash == MS_HASH_SHA3_256) launch_elements<4>(ctx, V, d_coin, d_elems, count);
         else launch_elements<1>(ctx, V, d_coin, d_elems, count);
     }
     HIPCHK(hipGetLastError());
@@ -218,6 +223,8 @@ extern "C" int ms_coin_pow_grind(ms_ctx* ctx, void* d_coin, unsigned bits, uint6
             ProfScope ps(ctx, "coin_pow_grind", 0.0);
             const dim3 grid((unsigned)((count + mscoin::NT - 1) / mscoin::NT)), block(mscoin::NT);
             if (hash == MS_HASH_SHA256) hipLaunchKernelGGL(mscoin::coin_pow_grind<0>, grid, block, 0, ctx->stream, (const State*)d_coin, base, count, bits, (unsigned long long*)d_found);
+            else if (hash == MS_HASH_KECCAK256) hipLaunchKernelGGL(mscoin::coin_pow_grind<3>, grid, block, 0, ctx->stream, (const State*)d_coin, base, count, bits, (unsigned long long*)d_found);
+            else if (hash == MS_HASH_SHA3_256) hipLaunchKernelGGL(mscoin::coin_pow_grind<4>, grid, block, 0, ctx->stream, (const State*)d_coin, base, count, bits, (unsigned long long*)d_found);
             else hipLaunchKernelGGL(mscoin::coin_pow_grind<1>, grid, block, 0, ctx->stream, (const State*)d_coin, base, count, bits, (unsigned long long*)d_found);
         }
         HIPCHK(hipMemcpyAsync(&found, d_found, 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -245,7 +245,7 @@ def _lowered(comp_expr, ncols, field=GOLDILOCKS_FP):
 def prove_phases(planner, trace, comp_expr, draws, blowup=4, folding=8, max_remainder_coeffs=64, grinding_bits=8, hash="sha256",
                  keep=False, ce_blowup=None, time_phases=True, field=GOLDILOCKS_FP):
     """trace: Matrix of Fp columns (2^k rows).  field: GOLDILOCKS_FP, or STARK252_FP (trace, draws and constraints over the 252-bit
-    field, LDE offset 3; commits with "sha256" or "blake2s" -- RPO-256 absorbs Goldilocks elements).  ce_blowup: the AIR's ce_blowup_factor (src/air.rs:55-59; the constraint
+    field, LDE offset 3; commits with "sha256", "blake2s", "keccak256" or "sha3_256" -- RPO-256 absorbs Goldilocks elements).  ce_blowup: the AIR's ce_blowup_factor (src/air.rs:55-59; the constraint
     evaluation domain has trace_len * ce_blowup points, the composition trace ce_blowup columns); None = the LDE blow-up.
     Returns dict(roots=..., fri_roots=[...], remainder=GpuVec, nonce=int, queries=Queries, phases_ms={...}); with keep=True
     also the intermediate device objects (for parity tests).  time_phases=False: no device wait at the phase boundaries (two of the six
@@ -254,7 +254,7 @@ def prove_phases(planner, trace, comp_expr, draws, blowup=4, folding=8, max_rema
     if field not in (GOLDILOCKS_FP, STARK252_FP):
         raise ValueError("prove_phases: field must be GOLDILOCKS_FP or STARK252_FP")
     if field == STARK252_FP and hash == "rpo256":
-        raise ValueError("prove_phases: RPO-256 absorbs Goldilocks elements; the 252-bit field commits with sha256 or blake2s")
+        raise ValueError("prove_phases: RPO-256 absorbs Goldilocks elements; the 252-bit field commits with sha256, blake2s, keccak256 or sha3_256")
     if field == STARK252_FP and trace.field != field:
         raise ValueError("prove_phases: field=STARK252_FP needs a trace over that field")
     h = field_generator(field)
@@ -381,7 +381,7 @@ def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, foldi
     if field not in (GOLDILOCKS_FP, STARK252_FP):
         raise ValueError("prove: field must be GOLDILOCKS_FP or STARK252_FP")
     if field == STARK252_FP and hash == "rpo256":
-        raise ValueError("prove: RPO-256 absorbs Goldilocks elements; the 252-bit field commits with sha256 or blake2s")
+        raise ValueError("prove: RPO-256 absorbs Goldilocks elements; the 252-bit field commits with sha256, blake2s, keccak256 or sha3_256")
     if trace.field != field:
         raise ValueError("prove: the trace is not over `field`")
     h = field_generator(field)

@@ -2,11 +2,12 @@
 //! (reference: gpu/src/plan.rs:32-174, 236-325, 327-351, 464-469).  Same names, same signatures on host slices; the
 //! `*_device` methods are the resident variants the patched callers use (rust/patches/).
 use super::sys;
+use super::sys_keccak;
 use super::utils::{field_id, DeviceVec};
 use crate::GpuField;
 use ark_poly::domain::Radix2EvaluationDomain;
 use ark_poly::EvaluationDomain;
-use core::ffi::c_void;
+use core::ffi::{c_int, c_void};
 use core::marker::PhantomData;
 use once_cell::sync::Lazy;
 
@@ -144,6 +145,18 @@ pub fn sha256_commit_device<F: GpuField>(columns: &[DeviceVec<F>]) -> (DeviceVec
     let cols: Vec<*const c_void> = columns.iter().map(|c| c.device_ptr() as *const c_void).collect();
     sys::check(unsafe { sys::ms_sha256_rows(get_planner().ctx(), field_id::<F>(), n, cols.as_ptr(), cols.len() as u32, leaves.device_ptr()) });
     sys::check(unsafe { sys::ms_sha256_merkle(get_planner().ctx(), n, leaves.device_ptr() as *const c_void, nodes.device_ptr()) });
+    (leaves, nodes)
+}
+
+/// `sha256_commit_device` with H = Keccak-256 (`sys_keccak::MS_KECCAK256`, the EVM's KECCAK256) or SHA3-256 (`sys_keccak::MS_SHA3_256`):
+/// the `Hash` arm of `MatrixMerkleTreeImpl<H>` for a proof an on-chain verifier checks.  -> (leaves, nodes); nodes[1] is the root.
+pub fn keccak_commit_device<F: GpuField>(variant: c_int, columns: &[DeviceVec<F>]) -> (DeviceVec<[u8; 32]>, DeviceVec<[u8; 32]>) {
+    let n = columns[0].len();
+    let leaves = DeviceVec::<[u8; 32]>::with_len(n);
+    let nodes = DeviceVec::<[u8; 32]>::with_len(n);
+    let cols: Vec<*const c_void> = columns.iter().map(|c| c.device_ptr() as *const c_void).collect();
+    sys::check(unsafe { sys_keccak::ms_keccak_rows(get_planner().ctx(), variant, field_id::<F>(), n, cols.as_ptr(), cols.len() as u32, leaves.device_ptr()) });
+    sys::check(unsafe { sys_keccak::ms_keccak_merkle(get_planner().ctx(), variant, n, leaves.device_ptr() as *const c_void, nodes.device_ptr()) });
     (leaves, nodes)
 }
 
