@@ -288,6 +288,15 @@ def _gather_digests(planner, digests, ndigests, ids):
 
 HASHES = ("sha256", "rpo256", "blake2s", "keccak256", "sha3_256")
 KECCAK_VARIANTS = {"keccak256": 0, "sha3_256": 1}          # MS_KECCAK256 / MS_SHA3_256 of include/ministark_hip_keccak.h
+# the byte hashes share one set of entry points, ms_<prefix>_{rows, rows_row_major, merkle, pow_grind}: name -> (prefix, leading arguments)
+_BYTE_HASHES = {"sha256": ("sha256", ()), "blake2s": ("blake2s", ()),
+                **{name: ("keccak", (variant,)) for name, variant in KECCAK_VARIANTS.items()}}
+
+
+def _byte_hash_call(planner, hash, op, *args):
+    """ms_<prefix>_<op>(ctx, <the hash's leading arguments>, *args), checked"""
+    prefix, lead = _BYTE_HASHES[hash]
+    planner.lib.check(getattr(planner.lib, f"ms_{prefix}_{op}")(planner.handle, *lead, *args))
 
 
 def merkle_view_ids(n, indices, lib=None):
@@ -374,15 +383,10 @@ class MerkleTree:
         self.nleaves = nleaves
         self.hash = hash
         self.nodes = DeviceBytes(planner, nleaves * 32)
-        L = planner.lib
-        if hash == "sha256":
-            L.check(L.ms_sha256_merkle(planner.handle, nleaves, leaves.ptr, self.nodes.ptr))
-        elif hash == "blake2s":
-            L.check(L.ms_blake2s_merkle(planner.handle, nleaves, leaves.ptr, self.nodes.ptr))
-        elif hash in KECCAK_VARIANTS:
-            L.check(L.ms_keccak_merkle(planner.handle, KECCAK_VARIANTS[hash], nleaves, leaves.ptr, self.nodes.ptr))
+        if hash == "rpo256":
+            planner.lib.check(planner.lib.ms_rpo256_merkle(planner.handle, nleaves, leaves.ptr, self.nodes.ptr))
         else:
-            L.check(L.ms_rpo256_merkle(planner.handle, nleaves, leaves.ptr, self.nodes.ptr))
+            _byte_hash_call(planner, hash, "merkle", nleaves, leaves.ptr, self.nodes.ptr)
 
     @classmethod
     def from_matrix(cls, matrix, hash="sha256"):
@@ -395,17 +399,13 @@ class MerkleTree:
         pl = evaluations.planner
         nrows = len(evaluations) // folding_factor
         leaves = DeviceBytes(pl, nrows * 32)
-        if hash == "sha256":
-            pl.lib.check(pl.lib.ms_sha256_rows_row_major(pl.handle, evaluations.field, nrows, folding_factor, evaluations.ptr, leaves.ptr))
-        elif hash == "rpo256":
+        if hash == "rpo256":
             if evaluations.field == STARK252_FP:
                 raise ValueError("RPO-256 absorbs Goldilocks elements")
             words = folding_factor * FIELD_WORDS[evaluations.field]          # a row is N elements = N (or 3 N) Fp words in memory order
             pl.lib.check(pl.lib.ms_rpo256_rows_row_major(pl.handle, nrows, words, evaluations.ptr, leaves.ptr))
-        elif hash == "blake2s":
-            pl.lib.check(pl.lib.ms_blake2s_rows_row_major(pl.handle, evaluations.field, nrows, folding_factor, evaluations.ptr, leaves.ptr))
-        elif hash in KECCAK_VARIANTS:
-            pl.lib.check(pl.lib.ms_keccak_rows_row_major(pl.handle, KECCAK_VARIANTS[hash], evaluations.field, nrows, folding_factor, evaluations.ptr, leaves.ptr))
+        elif hash in _BYTE_HASHES:
+            _byte_hash_call(pl, hash, "rows_row_major", evaluations.field, nrows, folding_factor, evaluations.ptr, leaves.ptr)
         else:
             raise ValueError(f"unknown hash {hash!r} (one of {HASHES})")
         return cls(pl, leaves, nrows, hash)
@@ -767,14 +767,10 @@ class Matrix:
         pl = self.planner
         n = self.num_rows()
         leaves = DeviceBytes(pl, n * 32)
-        if hash == "sha256":
-            pl.lib.check(pl.lib.ms_sha256_rows(pl.handle, self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr))
-        elif hash == "rpo256":
+        if hash == "rpo256":
             pl.lib.check(pl.lib.ms_rpo256_rows_field(pl.handle, self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr))
-        elif hash == "blake2s":
-            pl.lib.check(pl.lib.ms_blake2s_rows(pl.handle, self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr))
-        elif hash in KECCAK_VARIANTS:
-            pl.lib.check(pl.lib.ms_keccak_rows(pl.handle, KECCAK_VARIANTS[hash], self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr))
+        elif hash in _BYTE_HASHES:
+            _byte_hash_call(pl, hash, "rows", self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr)
         else:
             raise ValueError(f"unknown hash {hash!r} (one of {HASHES})")
         return leaves
@@ -939,13 +935,9 @@ def grind_proof_of_work(planner, seed, proof_of_work_bits, max_nonce=(1 << 40), 
     Keccak-256 ("keccak256") or SHA3-256 ("sha3_256")."""
     seed = bytes(seed)
     assert len(seed) == 32
-    if hash not in ("sha256", "blake2s") and hash not in KECCAK_VARIANTS:
+    if hash not in _BYTE_HASHES:
         raise ValueError(f"unknown proof-of-work hash {hash!r} (sha256, blake2s, keccak256 or sha3_256)")
     out = ctypes.c_uint64(0)
     buf = ctypes.create_string_buffer(seed, 32)
-    if hash in KECCAK_VARIANTS:
-        planner.lib.check(planner.lib.ms_keccak_pow_grind(planner.handle, KECCAK_VARIANTS[hash], buf, proof_of_work_bits, max_nonce, ctypes.byref(out)))
-        return out.value
-    grind = planner.lib.ms_blake2s_pow_grind if hash == "blake2s" else planner.lib.ms_sha256_pow_grind
-    planner.lib.check(grind(planner.handle, buf, proof_of_work_bits, max_nonce, ctypes.byref(out)))
+    _byte_hash_call(planner, hash, "pow_grind", buf, proof_of_work_bits, max_nonce, ctypes.byref(out))
     return out.value

@@ -210,7 +210,8 @@ static __global__ void __launch_bounds__(NT) blake2s_pow_grind(PowParams P) {
     #pragma unroll
     for (int q = 10; q < 16; q++) s.m[q] = 0;
     s.compress(40, true);
-    // leading zero bits of the digest's byte string: byte 0's high bit first, i.e. of each word read big-endian
+    // mshash::leading_zero_bits<false>(s.h), written out: through the function this kernel's register and instruction counts move
+    // (profiles/r10_kernel_resources*.txt)
     unsigned lz = 0;
     bool done = false;
     #pragma unroll

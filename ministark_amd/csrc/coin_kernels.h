@@ -57,7 +57,7 @@ __device__ __forceinline__ void hash_short(const uint32_t (&m)[16], unsigned len
             s.compress();
         } else {
             s.compress();
-            s.compress_pad64();
+            s.compress_kw(mssha::KW_PAD64);
         }
         #pragma unroll
         for (int q = 0; q < 8; q++) out[q] = mssha::bswap32(s.h[q]);
@@ -246,7 +246,9 @@ static __global__ void __launch_bounds__(NT) coin_pow_grind(const State* __restr
     uint32_t seed[8], d[8];
     load_digest(coin->seed, seed);
     merge_with_int<H>(seed, nonce, d);
-    unsigned lz = 0;                              // leading zero bits of the digest's byte string, byte 0's high bit first
+    // mshash::leading_zero_bits<false>(d), written out: through the function these kernels' instruction counts move
+    // (profiles/r10_kernel_resources*.txt)
+    unsigned lz = 0;
     bool done = false;
     #pragma unroll
     for (int q = 0; q < 8; q++) {

@@ -319,8 +319,44 @@ public:
 // merge), or the Keccak sponge as Keccak-256 (the EVM's KECCAK256) / SHA3-256 (any field; the same bytes, one permutation per merge).
 // All digests are 32 bytes, proofs have the same shape.
 enum class Hash { Sha256, Rpo256, Blake2s, Keccak256, Sha3_256 };
-inline bool is_keccak(Hash h) { return h == Hash::Keccak256 || h == Hash::Sha3_256; }
 inline int keccak_variant(Hash h) { return h == Hash::Sha3_256 ? MS_SHA3_256 : MS_KECCAK256; }        // `variant` of ms_keccak_*
+// One dispatch per operation: the entry point of `h` (the RPO-256 ones differ in shape: digests of field elements, rows counted in Fp words).
+inline int hash_rows(ms_ctx* ctx, Hash h, int field, size_t nrows, const void* const* d_cols, unsigned ncols, void* d_leaves) {
+    switch (h) {
+        case Hash::Sha256: return ms_sha256_rows(ctx, field, nrows, d_cols, ncols, d_leaves);
+        case Hash::Blake2s: return ms_blake2s_rows(ctx, field, nrows, d_cols, ncols, d_leaves);
+        case Hash::Keccak256: case Hash::Sha3_256: return ms_keccak_rows(ctx, keccak_variant(h), field, nrows, d_cols, ncols, d_leaves);
+        case Hash::Rpo256: break;
+    }
+    return ms_rpo256_rows_field(ctx, field, nrows, d_cols, ncols, d_leaves);
+}
+inline int hash_rows_row_major(ms_ctx* ctx, Hash h, int field, size_t nrows, unsigned ncols, const void* d_matrix, void* d_leaves) {
+    switch (h) {
+        case Hash::Sha256: return ms_sha256_rows_row_major(ctx, field, nrows, ncols, d_matrix, d_leaves);
+        case Hash::Blake2s: return ms_blake2s_rows_row_major(ctx, field, nrows, ncols, d_matrix, d_leaves);
+        case Hash::Keccak256: case Hash::Sha3_256: return ms_keccak_rows_row_major(ctx, keccak_variant(h), field, nrows, ncols, d_matrix, d_leaves);
+        case Hash::Rpo256: break;
+    }
+    return ms_rpo256_rows_row_major(ctx, nrows, ncols * (unsigned)(ms_field_bytes(field) / 8), d_matrix, d_leaves);
+}
+inline int hash_merkle(ms_ctx* ctx, Hash h, size_t nleaves, const void* d_leaves, void* d_nodes) {
+    switch (h) {
+        case Hash::Sha256: return ms_sha256_merkle(ctx, nleaves, d_leaves, d_nodes);
+        case Hash::Blake2s: return ms_blake2s_merkle(ctx, nleaves, d_leaves, d_nodes);
+        case Hash::Keccak256: case Hash::Sha3_256: return ms_keccak_merkle(ctx, keccak_variant(h), nleaves, d_leaves, d_nodes);
+        case Hash::Rpo256: break;
+    }
+    return ms_rpo256_merkle(ctx, nleaves, d_leaves, d_nodes);
+}
+// an RPO-256 prover grinds with SHA-256
+inline int hash_pow_grind(ms_ctx* ctx, Hash h, const void* h_seed32, unsigned bits, uint64_t max_nonce, uint64_t* nonce) {
+    switch (h) {
+        case Hash::Blake2s: return ms_blake2s_pow_grind(ctx, h_seed32, bits, max_nonce, nonce);
+        case Hash::Keccak256: case Hash::Sha3_256: return ms_keccak_pow_grind(ctx, keccak_variant(h), h_seed32, bits, max_nonce, nonce);
+        case Hash::Sha256: case Hash::Rpo256: break;
+    }
+    return ms_sha256_pow_grind(ctx, h_seed32, bits, max_nonce, nonce);
+}
 
 class MerkleTree {
 public:
@@ -328,10 +364,7 @@ public:
     static MerkleTree from_matrix(const Matrix<F>& m, Hash h = Hash::Sha256) {                // src/merkle.rs:356-361
         MerkleTree t(m.planner(), m.num_rows());
         std::vector<const void*> in; for (auto& c : m.columns) in.push_back(c.ptr());
-        if (h == Hash::Sha256) check(ms_sha256_rows(t.pl_->ctx(), F::id, t.n_, in.data(), (unsigned)in.size(), t.leaves_));
-        else if (h == Hash::Blake2s) check(ms_blake2s_rows(t.pl_->ctx(), F::id, t.n_, in.data(), (unsigned)in.size(), t.leaves_));
-        else if (is_keccak(h)) check(ms_keccak_rows(t.pl_->ctx(), keccak_variant(h), F::id, t.n_, in.data(), (unsigned)in.size(), t.leaves_));
-        else check(ms_rpo256_rows_field(t.pl_->ctx(), F::id, t.n_, in.data(), (unsigned)in.size(), t.leaves_));
+        check(hash_rows(t.pl_->ctx(), h, F::id, t.n_, in.data(), (unsigned)in.size(), t.leaves_));
         t.build(h);
         return t;
     }
@@ -340,10 +373,7 @@ public:
     template <class F>
     static MerkleTree from_fri_layer(const GpuVec<F>& evaluations, unsigned folding_factor, Hash h = Hash::Sha256) {
         MerkleTree t(evaluations.planner(), evaluations.len() / folding_factor);
-        if (h == Hash::Sha256) check(ms_sha256_rows_row_major(t.pl_->ctx(), F::id, t.n_, folding_factor, evaluations.ptr(), t.leaves_));
-        else if (h == Hash::Blake2s) check(ms_blake2s_rows_row_major(t.pl_->ctx(), F::id, t.n_, folding_factor, evaluations.ptr(), t.leaves_));
-        else if (is_keccak(h)) check(ms_keccak_rows_row_major(t.pl_->ctx(), keccak_variant(h), F::id, t.n_, folding_factor, evaluations.ptr(), t.leaves_));
-        else check(ms_rpo256_rows_row_major(t.pl_->ctx(), t.n_, folding_factor * (unsigned)(ms_field_bytes(F::id) / 8), evaluations.ptr(), t.leaves_));
+        check(hash_rows_row_major(t.pl_->ctx(), h, F::id, t.n_, folding_factor, evaluations.ptr(), t.leaves_));
         t.build(h);
         return t;
     }
@@ -402,12 +432,7 @@ public:
     MerkleTree(MerkleTree&& o) noexcept : pl_(o.pl_), n_(o.n_), leaves_(o.leaves_), nodes_(o.nodes_) { o.leaves_ = o.nodes_ = nullptr; }
 private:
     MerkleTree(Planner& pl, size_t n) : pl_(&pl), n_(n) { check(ms_alloc(pl.ctx(), n * 32, &leaves_)); check(ms_alloc(pl.ctx(), n * 32, &nodes_)); }
-    void build(Hash h) {
-        if (h == Hash::Sha256) check(ms_sha256_merkle(pl_->ctx(), n_, leaves_, nodes_));
-        else if (h == Hash::Blake2s) check(ms_blake2s_merkle(pl_->ctx(), n_, leaves_, nodes_));
-        else if (is_keccak(h)) check(ms_keccak_merkle(pl_->ctx(), keccak_variant(h), n_, leaves_, nodes_));
-        else check(ms_rpo256_merkle(pl_->ctx(), n_, leaves_, nodes_));
-    }
+    void build(Hash h) { check(hash_merkle(pl_->ctx(), h, n_, leaves_, nodes_)); }
     Pending gather_launch(const void* digests, const std::vector<uint64_t>& ids, GatherArena* arena) const {
         Pending out(*pl_, ids.size() * 32, arena);
         gather_digests_into(*pl_, digests, n_, ids, out.ptr(), arena);

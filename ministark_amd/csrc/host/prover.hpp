@@ -170,9 +170,7 @@ private:
 inline uint64_t grind_proof_of_work(Planner& pl, const std::array<uint8_t, 32>& seed, unsigned proof_of_work_bits, uint64_t max_nonce = (uint64_t)1 << 40,
                                     Hash h = Hash::Sha256) {
     uint64_t nonce = 0;
-    if (h == Hash::Blake2s) check(ms_blake2s_pow_grind(pl.ctx(), seed.data(), proof_of_work_bits, max_nonce, &nonce));
-    else if (is_keccak(h)) check(ms_keccak_pow_grind(pl.ctx(), keccak_variant(h), seed.data(), proof_of_work_bits, max_nonce, &nonce));
-    else check(ms_sha256_pow_grind(pl.ctx(), seed.data(), proof_of_work_bits, max_nonce, &nonce));
+    check(hash_pow_grind(pl.ctx(), h, seed.data(), proof_of_work_bits, max_nonce, &nonce));
     return nonce;
 }
 

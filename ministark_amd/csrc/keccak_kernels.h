@@ -31,6 +31,7 @@
 #include "gl_dev.h"
 #include "fp252.h"
 #include "keccak_sponge.h"
+#include "hash_dev.h"
 
 namespace mskec {
 
@@ -184,22 +185,6 @@ static __global__ void __launch_bounds__(NT) keccak_merkle_top(const uint8_t* __
 // atomicMin.  seed[] holds the 32 seed bytes as little-endian words (wave-uniform).
 struct PowParams { uint32_t seed[8]; unsigned long long base; unsigned long long count; unsigned bits; uint32_t domain; unsigned long long* found; };
 
-// leading zero bits of a digest's byte string: byte 0's high bit first, i.e. of each word read big-endian
-__device__ __forceinline__ unsigned leading_zero_bits(const uint32_t (&d)[8]) {
-    unsigned lz = 0;
-    bool done = false;
-    #pragma unroll
-    for (int q = 0; q < 8; q++) {
-        if (!done) {
-            const uint32_t w = __builtin_bswap32(d[q]);
-            const unsigned z = w ? (unsigned)__clz(w) : 32u;
-            lz += z;
-            if (z != 32) done = true;
-        }
-    }
-    return lz;
-}
-
 static __global__ void __launch_bounds__(NT) keccak_pow_grind(PowParams P) {
     const unsigned long long i = (unsigned long long)blockIdx.x * NT + threadIdx.x;
     if (i >= P.count) return;
@@ -215,7 +200,7 @@ static __global__ void __launch_bounds__(NT) keccak_pow_grind(PowParams P) {
     s.permute<UNROLL_WIDE>();
     uint32_t d[8];
     s.digest(d);
-    if (leading_zero_bits(d) >= P.bits) atomicMin(P.found, nonce);
+    if (mshash::leading_zero_bits<false>(d) >= P.bits) atomicMin(P.found, nonce);
 }
 
 }  // namespace mskec

@@ -4,6 +4,7 @@
 // points enqueue one single-wave launch and never wait.  Kernels and the rules they implement: coin_kernels.h.
 #include "ms_internal.h"
 #include "../../include/ministark_hip_keccak.h"
+#include "commit_host.h"
 #include "coin_kernels.h"
 
 using mscoin::State;
@@ -203,35 +204,17 @@ extern "C" int ms_coin_draw_queries(ms_ctx* ctx, void* d_coin, size_t max_n, siz
     return MS_OK;
 }
 
-// the windowed search of ms_sha256_pow_grind; the kernel takes the seed from the coin's state
+// the windowed search of commit_host.h; the kernel takes the seed from the coin's state
 extern "C" int ms_coin_pow_grind(ms_ctx* ctx, void* d_coin, unsigned bits, uint64_t max_nonce, uint64_t* nonce) {
     int hash = 0;
     MSCHK(coin_lookup(ctx, "ms_coin_pow_grind", d_coin, &hash));
     if (!nonce) return fail(MS_ERR_INVALID, "ms_coin_pow_grind: null argument");
-    if (bits > 64) return fail(MS_ERR_INVALID, "proof-of-work bits must be <= 64");
-    void* d_found = nullptr;
-    PoolGuard pooled(ctx);
-    MSCHK(pooled.alloc(8, &d_found));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    unsigned long long window = 1ull << 12;             // grows to 2^24 nonces per launch
-    unsigned long long none = ~0ull, found = ~0ull, count = 0;
-    for (unsigned long long base = 1; base <= max_nonce; base += count, window = std::min(window * 4, 1ull << 24)) {
-        count = std::min<unsigned long long>(window, max_nonce - base + 1);
-        HIPCHK(hipMemcpyAsync(d_found, &none, 8, hipMemcpyHostToDevice, ctx->stream));
-        {
-            ProfScope ps(ctx, "coin_pow_grind", 0.0);
-            const dim3 grid((unsigned)((count + mscoin::NT - 1) / mscoin::NT)), block(mscoin::NT);
-            if (hash == MS_HASH_SHA256) hipLaunchKernelGGL(mscoin::coin_pow_grind<0>, grid, block, 0, ctx->stream, (const State*)d_coin, base, count, bits, (unsigned long long*)d_found);
-            else if (hash == MS_HASH_KECCAK256) hipLaunchKernelGGL(mscoin::coin_pow_grind<3>, grid, block, 0, ctx->stream, (const State*)d_coin, base, count, bits, (unsigned long long*)d_found);
-            else if (hash == MS_HASH_SHA3_256) hipLaunchKernelGGL(mscoin::coin_pow_grind<4>, grid, block, 0, ctx->stream, (const State*)d_coin, base, count, bits, (unsigned long long*)d_found);
-            else hipLaunchKernelGGL(mscoin::coin_pow_grind<1>, grid, block, 0, ctx->stream, (const State*)d_coin, base, count, bits, (unsigned long long*)d_found);
-        }
-        HIPCHK(hipMemcpyAsync(&found, d_found, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (found != none) break;
-    }
-    if (found == none) return fail(MS_ERR_INVALID, "no nonce below %llu has %u leading zero bits", (unsigned long long)max_nonce, bits);
-    *nonce = found;
-    return MS_OK;
+    return mscommit::grind_windows(ctx, bits, max_nonce, "coin_pow_grind", [&](unsigned long long base, unsigned long long count, unsigned long long* found) {
+        const dim3 grid = mscommit::blocks_of(count, mscoin::NT), block(mscoin::NT);
+        const State* coin = (const State*)d_coin;
+        if (hash == MS_HASH_SHA256) hipLaunchKernelGGL(mscoin::coin_pow_grind<0>, grid, block, 0, ctx->stream, coin, base, count, bits, found);
+        else if (hash == MS_HASH_KECCAK256) hipLaunchKernelGGL(mscoin::coin_pow_grind<3>, grid, block, 0, ctx->stream, coin, base, count, bits, found);
+        else if (hash == MS_HASH_SHA3_256) hipLaunchKernelGGL(mscoin::coin_pow_grind<4>, grid, block, 0, ctx->stream, coin, base, count, bits, found);
+        else hipLaunchKernelGGL(mscoin::coin_pow_grind<1>, grid, block, 0, ctx->stream, coin, base, count, bits, found);
+    }, nonce);
 }

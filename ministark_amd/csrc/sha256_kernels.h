@@ -16,6 +16,7 @@
 #include "gl.h"
 #include "gl_dev.h"
 #include "fp252.h"
+#include "hash_dev.h"
 
 namespace mssha {
 
@@ -91,7 +92,7 @@ struct Sha {
         }
         h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
     }
-    // compression of a block whose 16 words are constants: kw[i] = K256[i] + W[i] precomputed (wave-uniform table)
+    // compression of a block whose 16 words are constants: kw[i] = K256[i] + W[i] precomputed (wave-uniform table; KW_PAD64: literals)
     __device__ __forceinline__ void compress_kw(const uint32_t* __restrict__ kw) {
         uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
         #pragma unroll
@@ -106,20 +107,21 @@ struct Sha {
         }
         h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
     }
-    // compression of the constant padding block that follows a 64-byte message
-    __device__ __forceinline__ void compress_pad64() {
-        uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
+    // H(64 bytes at p): the Merkle merge, the data block and the constant padding block that follows a 64-byte message
+    __device__ __forceinline__ void merge(const uint4* __restrict__ p) {
+        init();
         #pragma unroll
-        for (int i = 0; i < 64; i++) {
-            const uint32_t S1 = xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25));
-            const uint32_t ch = ch3(e, f, g);
-            const uint32_t t1 = hh + S1 + ch + KW_PAD64[i];
-            const uint32_t S0 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22));
-            const uint32_t mj = maj3(a, b, c);
-            const uint32_t t2 = S0 + mj;
-            hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+        for (int q = 0; q < 4; q++) {
+            const uint4 v = p[q];
+            w[4 * q] = bswap32(v.x); w[4 * q + 1] = bswap32(v.y); w[4 * q + 2] = bswap32(v.z); w[4 * q + 3] = bswap32(v.w);
         }
-        h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
+        compress();
+        compress_kw(KW_PAD64);
+    }
+    __device__ __forceinline__ void put(uint8_t* out) const {
+        uint4* o = (uint4*)out;
+        o[0] = make_uint4(bswap32(h[0]), bswap32(h[1]), bswap32(h[2]), bswap32(h[3]));
+        o[1] = make_uint4(bswap32(h[4]), bswap32(h[5]), bswap32(h[6]), bswap32(h[7]));
     }
 };
 
@@ -196,9 +198,7 @@ static __global__ void __launch_bounds__(NT) sha256_rows(RowsParams P) {
         s.compress();
     }
     if (P.fold_last) s.compress_kw(P.kw_last);
-    uint4* out = (uint4*)(P.leaves + r * 32);
-    out[0] = make_uint4(bswap32(s.h[0]), bswap32(s.h[1]), bswap32(s.h[2]), bswap32(s.h[3]));
-    out[1] = make_uint4(bswap32(s.h[4]), bswap32(s.h[5]), bswap32(s.h[6]), bswap32(s.h[7]));
+    s.put(P.leaves + r * 32);
 }
 
 // nodes[out0 + i] = SHA-256(src[2i] || src[2i+1]) for i < count; digests are 32 raw bytes
@@ -206,18 +206,8 @@ static __global__ void __launch_bounds__(NT) sha256_merge_level(const uint8_t* _
     const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
     if (i >= count) return;
     Sha s;
-    s.init();
-    const uint4* in = (const uint4*)(src + i * 64);
-    #pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint4 v = in[q];
-        s.w[4 * q] = bswap32(v.x); s.w[4 * q + 1] = bswap32(v.y); s.w[4 * q + 2] = bswap32(v.z); s.w[4 * q + 3] = bswap32(v.w);
-    }
-    s.compress();
-    s.compress_pad64();
-    uint4* out = (uint4*)(dst + i * 32);
-    out[0] = make_uint4(bswap32(s.h[0]), bswap32(s.h[1]), bswap32(s.h[2]), bswap32(s.h[3]));
-    out[1] = make_uint4(bswap32(s.h[4]), bswap32(s.h[5]), bswap32(s.h[6]), bswap32(s.h[7]));
+    s.merge((const uint4*)(src + i * 64));
+    s.put(dst + i * 32);
 }
 
 // The upper part of the tree in few launches: a level of <= 2^17 parents is latency-bound as a launch of its own (two dependent
@@ -238,7 +228,9 @@ static __global__ void __launch_bounds__(NT) sha256_merkle_top(const uint8_t* __
     unsigned mine = count < (unsigned)NT ? count : (unsigned)NT;          // nodes of the current level this workgroup computes
     size_t level = count;                                                 // nodes of the current level in the whole tree
     Sha s;
-    auto first = [&](size_t node) {                                       // parent `node` of the level of `count` parents, from src, written to its slot
+    // parent `node` of the level of `count` parents, from src.  Written out here, not Sha::merge: with the member this kernel's static
+    // instruction count moves (4 624 -> 4 623, 9 191 -> 9 190 VALU; profiles/r10_kernel_resources.txt holds the counts as they are).
+    auto first = [&](size_t node) {
         s.init();
         const uint4* in = (const uint4*)(src + node * 64);
         #pragma unroll
@@ -247,12 +239,7 @@ static __global__ void __launch_bounds__(NT) sha256_merkle_top(const uint8_t* __
             s.w[4 * q] = bswap32(v.x); s.w[4 * q + 1] = bswap32(v.y); s.w[4 * q + 2] = bswap32(v.z); s.w[4 * q + 3] = bswap32(v.w);
         }
         s.compress();
-        s.compress_pad64();
-    };
-    auto put = [&](size_t slot) {
-        uint4* out = (uint4*)(nodes + slot * 32);
-        out[0] = make_uint4(bswap32(s.h[0]), bswap32(s.h[1]), bswap32(s.h[2]), bswap32(s.h[3]));
-        out[1] = make_uint4(bswap32(s.h[4]), bswap32(s.h[5]), bswap32(s.h[6]), bswap32(s.h[7]));
+        s.compress_kw(KW_PAD64);
     };
     if constexpr (PER == 2) {                                            // count is a multiple of 2 NT here
         const size_t n0 = (size_t)b * 2 * NT + 2 * t;
@@ -260,29 +247,24 @@ static __global__ void __launch_bounds__(NT) sha256_merkle_top(const uint8_t* __
         const uint4* in2 = (const uint4*)(src + (n0 + 1) * 64);          // the level below was written by another launch, its lines come from memory
         #pragma unroll
         for (int q = 0; q < 4; q++) second[q] = in2[q];
-        first(n0); put(level + n0);
+        first(n0);
+        s.put(nodes + (level + n0) * 32);
         uint32_t left[8];
         #pragma unroll
         for (int q = 0; q < 8; q++) left[q] = s.h[q];
-        s.init();
-        #pragma unroll
-        for (int q = 0; q < 4; q++) {
-            s.w[4 * q] = bswap32(second[q].x); s.w[4 * q + 1] = bswap32(second[q].y); s.w[4 * q + 2] = bswap32(second[q].z); s.w[4 * q + 3] = bswap32(second[q].w);
-        }
-        s.compress();
-        s.compress_pad64();
-        put(level + n0 + 1);
+        s.merge(second);
+        s.put(nodes + (level + n0 + 1) * 32);
         #pragma unroll
         for (int q = 0; q < 8; q++) { s.w[8 + q] = s.h[q]; s.w[q] = left[q]; }
         level >>= 1;
         s.init();
         s.compress();
-        s.compress_pad64();
+        s.compress_kw(KW_PAD64);
     } else if (t < mine) first((size_t)b * NT + t);
     int cur = 0;
     for (;;) {
         if (t < mine) {
-            put(level + (size_t)b * mine + t);
+            s.put(nodes + (level + (size_t)b * mine + t) * 32);
             #pragma unroll
             for (int q = 0; q < 8; q++) lvl[cur][t * 8 + q] = s.h[q];         // big-endian words, ready for the next schedule
         }
@@ -294,7 +276,7 @@ static __global__ void __launch_bounds__(NT) sha256_merkle_top(const uint8_t* __
             for (int q = 0; q < 16; q++) s.w[q] = lvl[cur][t * 16 + q];
             s.init();
             s.compress();
-            s.compress_pad64();
+            s.compress_kw(KW_PAD64);
         }
         cur ^= 1;
     }
@@ -317,18 +299,7 @@ static __global__ void __launch_bounds__(NT) sha256_pow_grind(PowParams P) {
     s.w[8] = (uint32_t)(nonce >> 32); s.w[9] = (uint32_t)nonce;       // big-endian u64
     s.w[10] = 0x80000000u; s.w[11] = 0; s.w[12] = 0; s.w[13] = 0; s.w[14] = 0; s.w[15] = 320;
     s.compress();
-    // leading zero bits of the big-endian digest
-    unsigned lz = 0;
-    bool done = false;
-    #pragma unroll
-    for (int q = 0; q < 8; q++) {
-        if (!done) {
-            const unsigned z = s.h[q] ? (unsigned)__clz(s.h[q]) : 32u;
-            lz += z;
-            if (z != 32) done = true;
-        }
-    }
-    if (lz >= P.bits) atomicMin(P.found, nonce);
+    if (mshash::leading_zero_bits<true>(s.h) >= P.bits) atomicMin(P.found, nonce);       // the state holds the digest's big-endian words
 }
 
 }  // namespace mssha
