@@ -154,14 +154,19 @@ class Lib:
             "ms_keccak_merkle": (i, [vp, i, sz, vp, vp]),
             "ms_keccak_pow_grind": (i, [vp, i, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         }
+        # include/ministark_hip_ext.h: the extension columns between the two trace commitments
+        ext_sigs = {
+            "ms_build_extension_columns": (i, [vp, i, i, sz, c_void_pp, u, vp, u, vp, vp, u, c_void_pp]),
+        }
         self.optional = {}
-        for name, (res, args) in list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()):
+        for name, (res, args) in list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
         self.sigs = sigs
         self.transcript_sigs = transcript_sigs
         self.keccak_sigs = keccak_sigs
+        self.ext_sigs = ext_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

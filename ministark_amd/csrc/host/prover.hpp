@@ -2,6 +2,7 @@
 //   apply_drp                         src/fri.rs:526-567
 //   DeepPolyComposer                  src/composer.rs:17-188
 //   scan_affine / running_product     examples/brainfuck/trace.rs:108-289 (extension-column loops)
+//   ExtColumn / build_extension_columns   src/trace.rs build_extension_columns: every extension column in one call (ministark_hip_ext.h)
 //   Queries                           src/trace.rs:113-157
 //   grind_proof_of_work               src/random.rs:48-55
 //   PublicCoin                        src/random.rs:61-141, as ProverChannel uses it (src/channel.rs:46-100); state on the device
@@ -10,6 +11,7 @@
 #pragma once
 #include "ministark.hpp"
 #include "../../../include/ministark_hip_transcript.h"
+#include "../../../include/ministark_hip_ext.h"
 #include <stdint.h>
 // host arithmetic of the 252-bit field (points and offsets of its composer): the library's own fp252.h, kept inside ms:: so that its
 // Goldilocks namespace does not meet ms::gl in a program that says `using namespace ms`
@@ -92,6 +94,38 @@ inline GpuVec<F> scan_affine(const GpuVec<F>* a, const GpuVec<F>* b, const std::
     return out;
 }
 template <class F> inline GpuVec<F> running_product(const GpuVec<F>& factors, const std::vector<uint64_t>& init) { return scan_affine<F>(&factors, nullptr, init); }
+
+// Trace::build_extension_columns(&challenges) in one asynchronous call (ms_build_extension_columns): per column
+//     state = init;  for row i: out[i] = state;  if active(i): state = A(i) * state + B(i),   A(i) = sum_t sign_t coef_t base[col_t][(i + off_t) mod n]
+// chal: an index into the challenge vector, or MS_EXT_NONE for the literal 1; col: an index into the base matrix, or MS_EXT_NONE for a constant term
+struct ExtTerm { int sign; int chal; int col; int off = 0; };
+struct ExtColumn {
+    int init = MS_EXT_INIT_ZERO, init_chal = 0;                  // MS_EXT_INIT_ZERO / _ONE / _CHALLENGE (the state starts as challenges[init_chal])
+    std::vector<ExtTerm> a_terms, b_terms;                       // an empty A is 1, an empty B is 0
+    int mask = MS_EXT_ALWAYS, mask_col = 0;                      // MS_EXT_IF_NONZERO / MS_EXT_IF_ZERO: active where base[mask_col][i] != 0 / == 0
+    bool inclusive = false;                                      // out[i] is the state AFTER row i
+};
+// base: columns of B (Fp or Fp252); challenges: elements of FqT on the device (e.g. PublicCoin::draw), or null when nothing names one.
+// Pairs Fp -> Fq3, Fp -> Fp, Fp252 -> Fp252.  Enqueues and returns.
+template <class FqT, class B>
+inline Matrix<FqT> build_extension_columns(const Matrix<B>& base, const GpuVec<FqT>* challenges, const std::vector<ExtColumn>& columns) {
+    Planner& pl = base.planner();
+    const size_t n = base.num_rows();
+    std::vector<ms_ext_column> recs;
+    std::vector<ms_ext_term> terms;
+    for (auto& c : columns) {
+        recs.push_back({c.init, c.init_chal, c.mask, c.mask_col, c.inclusive ? 1 : 0, (uint32_t)c.a_terms.size(), (uint32_t)c.b_terms.size(), 0});
+        for (auto* list : {&c.a_terms, &c.b_terms}) for (auto& t : *list) terms.push_back({t.col, t.off, t.chal, t.sign});
+    }
+    std::vector<const void*> in;
+    for (auto& c : base.columns) in.push_back(c.ptr());
+    Matrix<FqT> out;
+    std::vector<void*> outs;
+    for (size_t e = 0; e < columns.size(); e++) { out.columns.emplace_back(pl, n); outs.push_back(out.columns.back().ptr()); }
+    check(ms_build_extension_columns(pl.ctx(), B::id, FqT::id, n, in.data(), (unsigned)in.size(), challenges ? challenges->ptr() : nullptr,
+                                     challenges ? (unsigned)challenges->len() : 0u, recs.data(), terms.data(), (unsigned)columns.size(), outs.data()));
+    return out;
+}
 
 // `fold_positions` (src/fri.rs:615-622): strictly increasing positions -> their cosets, deduplicated
 inline std::vector<size_t> fold_positions(const std::vector<size_t>& positions, unsigned folding_factor) {

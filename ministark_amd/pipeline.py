@@ -70,12 +70,12 @@ def constraint_blowup_factor(c, trace_len):
     return _ceil_power_of_two(max(n - d, 0)) // (trace_len - 1)
 
 
-def composition_constraint(trace_len, constraints):
+def composition_constraint(trace_len, constraints, num_air_challenges=0, min_ce_blowup=1):
     """`AirConfig::composition_constraint` (src/air.rs:50-82): sum_i c_i (X^adj_i alpha_i + beta_i) with
-    adj_i = (trace_len ce_blowup - 1) - (deg num_i - deg den_i).  CompositionCoeff(i) is Challenge(i) here (the AIRs this
-    module drives have no other challenges; eval_constraint substitutes them as constants, src/air.rs:96-101).
-    Returns (expression, ce_blowup_factor, number of composition coefficients)."""
-    ce = max(constraint_blowup_factor(c, trace_len) for c in constraints)
+    adj_i = (trace_len ce_blowup - 1) - (deg num_i - deg den_i).  CompositionCoeff(i) is Challenge(num_air_challenges + i) here: the AIR's own
+    challenges come first, as `prove` draws them first (eval_constraint substitutes both as constants, src/air.rs:96-101).
+    min_ce_blowup: a floor for the constraint-evaluation blow-up.  Returns (expression, ce_blowup_factor, number of composition coefficients)."""
+    ce = max(min_ce_blowup, max(constraint_blowup_factor(c, trace_len) for c in constraints))
     composition_degree = trace_len * ce - 1
     x = E.X()
     comp = None
@@ -83,7 +83,7 @@ def composition_constraint(trace_len, constraints):
         n, d = _degree(c, trace_len - 1)
         assert n - d <= composition_degree
         adj = composition_degree - (n - d)
-        term = c * (x ** adj * E.Challenge(2 * i) + E.Challenge(2 * i + 1))
+        term = c * (x ** adj * E.Challenge(num_air_challenges + 2 * i) + E.Challenge(num_air_challenges + 2 * i + 1))
         comp = term if comp is None else comp + term
     return comp, ce, 2 * len(constraints)
 
@@ -113,6 +113,46 @@ def fib_constraints(n_trace, ncols=8, field=GOLDILOCKS_FP):
     composition polynomial has n coefficients and one column (src/prover.rs:111-124)."""
     assert ncols == 8, "examples/fib has 8 columns"
     return composition_constraint(n_trace, fib_air_constraints(n_trace, field))
+
+
+PERMUTATION_ROTATION = 5
+
+
+def permutation_trace(n, seed):
+    """A valid base trace of `permutation_air`: columns x0, x1, y0, y1 as canonical integers.  The y rows of 0..n-2 are the x rows of 0..n-2
+    cyclically rotated by PERMUTATION_ROTATION; row n-1 is padding (the running products stop in front of it)."""
+    rng = np.random.default_rng(seed)
+    x = [[int(v) for v in rng.integers(0, GL_P, size=n, dtype=np.uint64)] for _ in range(2)]
+    pad = [int(v) for v in rng.integers(0, GL_P, size=2, dtype=np.uint64)]
+    m = n - 1
+    y = [[col[(i + PERMUTATION_ROTATION) % m] for i in range(m)] + [pad[k]] for k, col in enumerate(x)]
+    return x + y
+
+
+def permutation_air(n):
+    """A small AIR with an extension trace, valid on `permutation_trace`: the rows (y0, y1) are a permutation of the rows (x0, x1), shown by
+    two running products over challenges drawn after the base commitment, plus a running evaluation of x0 (the three shapes of
+    examples/brainfuck/trace.rs:108-289).  Base columns 0..3 = x0, x1, y0, y1; extension columns 4..6 = P, Q, E; challenges 0..3 = alpha,
+    beta, gamma, delta:
+        P' = P (alpha - beta x0 - gamma x1)      Q' = Q (alpha - beta y0 - gamma y1)      E' = delta E + x0'
+    P = Q = 1 and E = 0 at row 0, P = Q at row n-1; the transitions hold on rows 0..n-2 (divided by (X^n - 1) / (X - g^(n-1))).
+    -> (composition constraint, ce_blowup 2, number of composition coefficients, number of AIR challenges 4, the ExtColumn records)."""
+    from .extension import ExtColumn
+    x = E.X()
+    dom = Radix2EvaluationDomain(n, 1, GOLDILOCKS_FP)
+    last_x = pow(dom.group_gen, n - 1, dom.p)
+    cur, nxt, ch = (lambda k: E.Trace(k, 0)), (lambda k: E.Trace(k, 1)), E.Challenge
+    P, Q, EV = 4, 5, 6
+    boundary = [(cur(P) - E.Constant(1)) / (x - E.Constant(1)), (cur(Q) - E.Constant(1)) / (x - E.Constant(1)), cur(EV) / (x - E.Constant(1))]
+    terminal = [(cur(P) - cur(Q)) / (x - E.Constant(last_x))]
+    tr = [nxt(P) - cur(P) * (ch(0) - ch(1) * cur(0) - ch(2) * cur(1)),
+          nxt(Q) - cur(Q) * (ch(0) - ch(1) * cur(2) - ch(2) * cur(3)),
+          nxt(EV) - (ch(3) * cur(EV) + nxt(0))]
+    zer = (x - E.Constant(last_x)) / (x ** n - E.Constant(1))
+    comp, ce, ncoeffs = composition_constraint(n, boundary + terminal + [t * zer for t in tr], num_air_challenges=4, min_ce_blowup=2)
+    product = lambda c0, c1: ExtColumn(1, [(+1, 0, None), (-1, 1, c0), (-1, 2, c1)], [])
+    columns = [product(0, 1), product(2, 3), ExtColumn(0, [(+1, 3, None)], [(+1, None, 0, 1)])]
+    return comp, ce, ncoeffs, 4, columns
 
 
 def additive_constraints(n_trace, ncols=8, ce_blowup=4):
@@ -229,15 +269,15 @@ def fri_num_layers(n_lde, blowup, folding, max_remainder_coeffs):
 _LOWERED = {}
 
 
-def _lowered(comp_expr, ncols, field=GOLDILOCKS_FP):
+def _lowered(comp_expr, ncols, field=GOLDILOCKS_FP, fq_is_ext=False):
     """The register program of an AIR's composition constraint, lowered once per expression object (an AIR's constraints are fixed; the
     C++ example compiles its program outside the proof loop as well).  Keyed by identity: the expression is kept alive by the entry."""
-    key = (id(comp_expr), ncols, field)
+    key = (id(comp_expr), ncols, field, fq_is_ext)
     hit = _LOWERED.get(key)
     if hit is None or hit[0] is not comp_expr:
         if len(_LOWERED) > 16:
             _LOWERED.clear()
-        hit = (comp_expr, E.compile_expr(comp_expr, ncols, False, field))
+        hit = (comp_expr, E.compile_expr(comp_expr, ncols, fq_is_ext, field))
         _LOWERED[key] = hit
     return hit[1]
 
@@ -361,25 +401,55 @@ def from_mont_words(field, words):
     return [gl_from_mont(int(x)) for x in w]
 
 
+def fq_words(fq, values):
+    """canonical values of `fq` (ints; 3-tuples or ints for Fq3, an int being embedded) -> their Montgomery words, one row per element"""
+    from .api import GOLDILOCKS_FQ3
+    if fq != GOLDILOCKS_FQ3:
+        return to_mont_words(fq, values)
+    return np.array([[gl_to_mont(c) for c in (v if isinstance(v, tuple) else (v, 0, 0))] for v in values], dtype=np.uint64).reshape(-1, 3)
+
+
+def from_fq_words(fq, words):
+    """Montgomery words of `fq` elements (flat) -> canonical values: ints, or 3-tuples for Fq3"""
+    from .api import GOLDILOCKS_FQ3
+    vals = from_mont_words(GOLDILOCKS_FP if fq == GOLDILOCKS_FQ3 else fq, words)
+    return [tuple(vals[i:i + 3]) for i in range(0, len(vals), 3)] if fq == GOLDILOCKS_FQ3 else vals
+
+
 def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, folding=8, max_remainder_coeffs=64, grinding_bits=8,
-          num_queries=32, hash="sha256", keep=False, ce_blowup=None, field=GOLDILOCKS_FP, trace_args=None):
+          num_queries=32, hash="sha256", keep=False, ce_blowup=None, field=GOLDILOCKS_FP, trace_args=None, fq=None, num_air_challenges=0,
+          extension=None):
     """The phases of `prove_phases` with every challenge drawn from the transcript: a device-resident `coin.PublicCoin` seeded with
     `seed32` (the digest of the public inputs, src/channel.rs:33-44) stands where `Draws` stood, in the reference's order
     (src/prover.rs:50-173, src/channel.rs:46-100, src/fri.rs:199-247):
-        commit base trace -> draw the `nchallenges` composition coefficients        commit composition trace -> draw z
+        commit base trace -> draw the `num_air_challenges` challenges of the AIR     build + commit the extension trace (if any)
+        draw the `nchallenges` composition coefficients                             commit composition trace -> draw z
         OOD evaluations -> reseed (execution, then composition)                     draw the DEEP coefficients (src/stark.rs:41-53)
         per FRI layer: commit -> reseed with the root -> draw alpha -> fold         remainder coefficients -> reseed
         grind -> reseed with the nonce                                              draw the query positions -> openings
+    fq: the field every challenge is drawn from and the composition, DEEP and FRI phases work over: `field` (the default), or
+    GOLDILOCKS_FQ3 over Goldilocks -- the reference's own choice for its Goldilocks AIRs, with or without an extension trace.
+    extension: a list of `extension.ExtColumn` -- the columns are built by ms_build_extension_columns from the challenges where the coin
+    drew them, and everything up to the extension commitment is enqueued without a host wait -- or a callable
+    (base_trace, challenges GpuVec) -> Matrix of `fq` columns.  The composition constraint numbers the AIR's challenges first, then the
+    composition coefficients (`composition_constraint(..., num_air_challenges=k)`); trace columns are numbered base | extension.
     The FRI commit phase is enqueued without a host wait: a layer's root is absorbed where the tree builder wrote it, alpha is drawn into
     device memory and the fold reads it there (ms_fri_fold_dev); roots and alphas are downloaded once, after the remainder.  The draws the
-    host itself needs (composition coefficients, z, DEEP coefficients) are downloaded where they are needed, as the reference's are.
-    Fq = Fp AIRs over Goldilocks or the 252-bit field; hints: canonical integers; H of the coin: BLAKE2s for a BLAKE2s prover, else SHA-256.
-    Returns what prove_phases returns (without timings), plus the draws as canonical integers: challenges, z, deep, fri_alphas, positions."""
-    from .api import GatherBatch, GpuVec
+    host itself needs (challenges and composition coefficients for the evaluator, z, DEEP coefficients) are downloaded where they are needed,
+    as the reference's are.  hints: canonical integers; H of the coin: BLAKE2s for a BLAKE2s prover, else SHA-256.
+    Returns what prove_phases returns (without timings), plus the draws as canonical values (3-tuples when fq is Fq3): air_challenges,
+    challenges (the composition coefficients), z, deep, fri_alphas, positions; `extension_root` when there is an extension trace.  keep=True
+    adds the intermediate device objects of prove_phases, `ext_trace` / `ext_polys` / `ext_lde`, the coin, and `remainder_poly`: all n_rem
+    coefficients of the remainder's interpolant, of which `remainder_coeffs` are the first n_rem / blowup (fri.rs:244 asserts the rest vanish)."""
+    from .api import FIELD_WORDS, GOLDILOCKS_FQ3, GatherBatch, GpuVec
     from .coin import PublicCoin
+    from .extension import build_extension_columns
     pl = planner
     if field not in (GOLDILOCKS_FP, STARK252_FP):
         raise ValueError("prove: field must be GOLDILOCKS_FP or STARK252_FP")
+    fq = field if fq is None else fq
+    if fq != field and (fq != GOLDILOCKS_FQ3 or field != GOLDILOCKS_FP):
+        raise ValueError("prove: fq is the base field, or GOLDILOCKS_FQ3 over GOLDILOCKS_FP")
     if field == STARK252_FP and hash == "rpo256":
         raise ValueError("prove: RPO-256 absorbs Goldilocks elements; the 252-bit field commits with sha256, blake2s, keccak256 or sha3_256")
     if trace.field != field:
@@ -391,9 +461,7 @@ def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, foldi
     assert ce_blowup <= blowup                                                 # src/air.rs:149
     n_ce = n_t * ce_blowup
     trace_dom, lde_dom, ce_dom = Radix2EvaluationDomain(n_t, 1, field), Radix2EvaluationDomain(n_lde, h, field), Radix2EvaluationDomain(n_ce, h, field)
-    prog = _lowered(comp_expr, trace.num_cols(), field)
-    trace_args = [(c, o) for c in range(trace.num_cols()) for o in (0, 1)] if trace_args is None else list(trace_args)
-    V = 4 if field == STARK252_FP else 1
+    V = FIELD_WORDS[fq]
     coin = PublicCoin(pl, seed32, pow_hash(hash))
     out = {}
 
@@ -401,42 +469,65 @@ def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, foldi
     lde_t = base_polys.bit_reversed_evaluate(lde_dom)
     tree_t = MerkleTree.from_matrix(lde_t, hash)
     coin.reseed_digest(tree_t.root_ptr())                                      # channel.commit_base_trace
-    ch = coin.draw(field, nchallenges).to_numpy().reshape(-1, V)               # air.get_challenges + composition coefficients (stark.rs:27-39)
-    comp_evals = E.eval(prog, pl, ch, to_mont_words(field, hints), ce_blowup, h, n_ce, lde_t.columns, bit_reversed=True)
+    air_ch = coin.draw(fq, num_air_challenges) if num_air_challenges else None  # air.get_challenges (prover.rs:56-58): left on the device
+    ext_trace = ext_polys = ext_lde = ext_tree = None
+    if extension is not None:                                                  # prover.rs:59-72
+        ext_trace = extension(trace, air_ch) if callable(extension) else build_extension_columns(pl, trace, air_ch, extension, fq)
+        if ext_trace.num_rows() != n_t or ext_trace.field != fq:
+            raise ValueError("prove: the extension trace has as many rows as the base trace and is over `fq`")
+        ext_polys = ext_trace.interpolate(trace_dom)
+        ext_lde = ext_polys.bit_reversed_evaluate(lde_dom)
+        ext_tree = MerkleTree.from_matrix(ext_lde, hash)
+        coin.reseed_digest(ext_tree.root_ptr())                                # channel.commit_extension_trace
+    nbase, next_ = trace.num_cols(), ext_trace.num_cols() if ext_trace is not None else 0
+    trace_args = [(c, o) for c in range(nbase + next_) for o in (0, 1)] if trace_args is None else list(trace_args)
+    coeffs = coin.draw(fq, nchallenges)                                        # the composition coefficients (stark.rs:27-39)
+    ch = coeffs.to_numpy().reshape(-1, V)
+    if air_ch is not None:
+        ch = np.concatenate([air_ch.to_numpy().reshape(-1, V), ch])
+    ext_cols = list(ext_lde.columns) if ext_lde is not None else []
+    if fq == field:                                                            # Fq = Fp: the interaction columns are base columns to the evaluator
+        prog = _lowered(comp_expr, nbase + next_, field)
+        comp_evals = E.eval(prog, pl, ch, fq_words(fq, hints), ce_blowup, h, n_ce, lde_t.columns + ext_cols, bit_reversed=True)
+    else:
+        prog = _lowered(comp_expr, nbase, field, True)
+        comp_evals = E.eval(prog, pl, ch, fq_words(fq, hints), ce_blowup, h, n_ce, lde_t.columns, ext_cols, bit_reversed=True)
     kept_evals = comp_evals.clone() if keep else None
     comp_poly = Matrix([comp_evals]).bit_reverse_rows().into_polynomials(ce_dom).columns[0]
     comp_polys = Matrix.from_chunks(comp_poly, ce_blowup)
     comp_lde = comp_polys.bit_reversed_evaluate(lde_dom)
     tree_c = MerkleTree.from_matrix(comp_lde, hash)
     coin.reseed_digest(tree_c.root_ptr())                                      # channel.commit_composition_trace
-    z = from_mont_words(field, coin.draw(field, 1).to_numpy())[0]              # channel.get_ood_point
-    composer = DeepPolyComposer(trace_args, n_t, z, base_polys, None, comp_polys)
+    z = from_fq_words(fq, coin.draw(fq, 1).to_numpy())[0]                      # channel.get_ood_point
+    composer = DeepPolyComposer(trace_args, n_t, z, base_polys, ext_polys, comp_polys)
     out["ood"] = composer.get_ood_evals()
-    coin.reseed_elements(to_mont_words(field, list(out["ood"][0]) + list(out["ood"][1])), field)       # channel.send_ood_evals: execution, composition
-    d = from_mont_words(field, coin.draw(field, len(trace_args) + ce_blowup + 2).to_numpy())           # stark.rs:41-53
+    coin.reseed_elements(fq_words(fq, list(out["ood"][0]) + list(out["ood"][1])), fq)                  # channel.send_ood_evals: execution, composition
+    d = from_fq_words(fq, coin.draw(fq, len(trace_args) + ce_blowup + 2).to_numpy())                   # stark.rs:41-53
     deep_coeffs = DeepCompositionCoeffs(d[: len(trace_args)], d[len(trace_args): len(trace_args) + ce_blowup], (d[-2], d[-1]))
     deep_poly = composer.into_deep_poly(deep_coeffs) if keep else None
-    deep = Matrix([composer.into_deep_evaluations(deep_coeffs, lde_t, None, comp_lde, n_lde)])
+    deep = Matrix([composer.into_deep_evaluations(deep_coeffs, lde_t, ext_lde, comp_lde, n_lde)])
     # fri.rs:179-231: nothing below waits for the device until the remainder is reseeded
     cur, n, layers, fri_trees, alphas = deep.columns[0], n_lde, [], [], []
     for _ in range(fri_num_layers(n_lde, blowup, folding, max_remainder_coeffs)):
         tree = MerkleTree.from_fri_layer(cur, folding, hash)
         coin.reseed_digest(tree.root_ptr())                                    # channel.commit_fri_layer (fri.rs:217-223)
-        alpha = coin.draw(field, 1)                                            # channel.draw_fri_alpha (fri.rs:225-227)
+        alpha = coin.draw(fq, 1)                                               # channel.draw_fri_alpha (fri.rs:225-227)
         layers.append(cur); fri_trees.append(tree); alphas.append(alpha)
         cur = apply_drp(cur, alpha, folding, 1)
         n //= folding
     rem = Matrix([cur.clone()]).bit_reverse_rows().into_polynomials(Radix2EvaluationDomain(n, 1, field)).columns[0]
     nrem = max(n // blowup, 1)
-    coin.reseed_elements(GpuVec(pl, nrem, field, ptr=rem.ptr))                 # channel.commit_remainder (fri.rs:232-248)
+    coin.reseed_elements(GpuVec(pl, nrem, fq, ptr=rem.ptr))                    # channel.commit_remainder (fri.rs:232-248)
     out["base_root"], out["composition_root"] = tree_t.root(), tree_c.root()
+    if ext_tree is not None:
+        out["extension_root"] = ext_tree.root()
     out["fri_roots"], out["remainder"] = [t.root() for t in fri_trees], cur
     out["remainder_coeffs"] = rem.to_numpy()[: nrem * V]
     out["nonce"] = coin.grind(grinding_bits)                                   # prover.rs:160, channel.rs:76-93
     coin.reseed_int(out["nonce"])
     positions = coin.draw_queries(num_queries, n_lde)                          # channel.get_fri_query_positions (prover.rs:161)
     batch = GatherBatch(pl)
-    queries = Queries(lde_t, None, comp_lde, tree_t, None, tree_c, positions, batch)                    # prover.rs:163-173
+    queries = Queries(lde_t, ext_lde, comp_lde, tree_t, ext_tree, tree_c, positions, batch)             # prover.rs:163-173
     pos, launched = positions, []
     for layer, tree in zip(layers, fri_trees):
         pos = fold_positions(pos, folding)
@@ -444,9 +535,12 @@ def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, foldi
     batch.fetch()
     out["queries"] = queries.fetch()
     out["fri_openings"] = [{"positions": p, "rows": rows(), "proof": proof()} for p, rows, proof in launched]
-    out.update(challenges=from_mont_words(field, ch), z=z, deep=deep_coeffs, positions=positions, trace_args=trace_args,
-               fri_alphas=[from_mont_words(field, a.to_numpy())[0] for a in alphas])
+    out.update(challenges=from_fq_words(fq, coeffs.to_numpy()), z=z, deep=deep_coeffs, positions=positions, trace_args=trace_args,
+               air_challenges=from_fq_words(fq, air_ch.to_numpy()) if air_ch is not None else [],
+               fri_alphas=[from_fq_words(fq, a.to_numpy())[0] for a in alphas])
     if keep:
         out.update(base_polys=base_polys, lde=lde_t, comp_evals=kept_evals, comp_polys=comp_polys, comp_lde=comp_lde,
-                   deep_poly=deep_poly, deep_lde=deep, fri_layers=layers, coin=coin)
+                   deep_poly=deep_poly, deep_lde=deep, fri_layers=layers, coin=coin, remainder_poly=rem)
+        if ext_trace is not None:
+            out.update(ext_trace=ext_trace, ext_polys=ext_polys, ext_lde=ext_lde)
     return out

@@ -21,6 +21,7 @@ pub mod plan;
 pub mod stage;
 pub mod sys;
 pub mod sys_keccak;
+pub mod sys_ext;
 pub mod sys_transcript;
 pub mod utils;
 
