@@ -181,7 +181,8 @@ int ms_lde(ms_ctx* ctx, int field, unsigned log_n, unsigned log_blowup, const vo
  * (untouched unless d_out[c] aliases it), d_out[c] receives 2^log_domain evaluations on coset(2^log_domain,
  * h_offset), optionally in bit-reversed order.  Blow-ups 4..16 never materialise the zero padding.
  * ms_deinterleave: `composition_poly.chunks(k)` spread over k columns (src/prover.rs:113-121):
- * d_out[c][j] = d_in[j*k + c], j < n_out. */
+ * d_out[c][j] = d_in[j*k + c], j < n_out, 1 <= k <= 128.  Every output column (n_out elements) is disjoint from d_in (n_out * k
+ * elements) and from the other output columns: anything else is MS_ERR_INVALID ("... overlap ...") before anything is enqueued. */
 int ms_evaluate(ms_ctx* ctx, int field, unsigned log_n, unsigned log_domain, const void* h_offset,
                 const void* const* d_in, void* const* d_out, unsigned ncols, int bit_reversed);
 int ms_deinterleave(ms_ctx* ctx, int field, size_t n_out, unsigned k, const void* d_in, void* const* d_out);
@@ -200,6 +201,11 @@ int ms_deinterleave(ms_ctx* ctx, int field, size_t n_out, unsigned k, const void
  *   ms_convert                 equal fields: d_dst == d_src is a no-op, disjoint buffers are copied, a partial overlap is
  *                              refused; Fp -> Fq3: any overlap is refused (there is no in-place embedding)
  *   ms_sum_columns             d_dst == a column or disjoint from it, for every column; columns may alias each other
+ * The same rule, with the same refusal, holds away from the stages:
+ *   ms_scan_affine             d_out == d_a or disjoint from it, and the same for d_b (n elements each); d_a and d_b are only
+ *                              read and may overlap each other in any way
+ *   ms_gather_rows, ms_gather_digests[_multi], ms_deinterleave
+ *                              no in-place form: every output is disjoint from every source range and from the other outputs
  *   ms_binary       MulAssign / MulInto / AddAssign / AddInto            (stage.rs:115-233, 393-521)
  *   ms_binary_const  {Mul,Add}{Into,Assign}Const                          (stage.rs:523-806)
  *   ms_mul_pow       MulPowStage: dst = lhs * rhs[(i+shift)%n]^power      (stage.rs:334-391)
@@ -343,11 +349,16 @@ int ms_eval_jit_stats(ms_ctx* ctx, ms_jit_stats* out);
  *                        state = init;  for i in 0..n:  out[i] = state;  state = a[i]*state + b[i]
  *                    (inclusive != 0: out[i] = the state AFTER row i).  d_a NULL = all ones (running sum),
  *                    d_b NULL = all zeros (running product); masked rows are a = 1, b = 0.  a, b, init, out
- *                    are elements of `field` (any of the three); out may alias a or b.  Any n >= 0.
+ *                    are elements of `field` (any of the three).  Any n >= 0.  d_out may BE d_a or d_b (or both: the same
+ *                    address); a d_out that overlaps d_a or d_b in any other way is MS_ERR_INVALID ("... overlap ...")
+ *                    before anything is enqueued.  d_a and d_b may overlap each other.
  * ms_gather_rows     out[p][c] = cols[c][positions[p]], row-major: Matrix::get_row over the query
- *                    positions (src/trace.rs:139-152, src/matrix.rs get_row)
+ *                    positions (src/trace.rs:139-152, src/matrix.rs get_row).  1..128 columns of nrows elements.  d_out
+ *                    (npos * ncols elements) must not overlap any column: MS_ERR_INVALID ("... overlap ..."), nothing enqueued;
+ *                    npos == 0 is MS_OK whatever the pointers.
  * ms_gather_digests  out[k] = digests[indices[k]] (32-byte records): the leaves / sibling leaves / nodes
- *                    a batched Merkle opening lists (MerkleTreeImpl::prove, src/merkle.rs:149-206)
+ *                    a batched Merkle opening lists (MerkleTreeImpl::prove, src/merkle.rs:149-206).  d_out (count records) must
+ *                    not overlap d_digests (ndigests records): MS_ERR_INVALID ("... overlap ..."), nothing enqueued.
  * ms_merkle_view_ids the index walk of MerkleTreeImpl::prove itself (src/merkle.rs:149-206; host-only, no device work): for a tree of
  *                    nleaves leaves and the queried leaf indices -> h_leaf_ids (the leaves to fetch: each queried leaf followed by its
  *                    pair partner or its sibling; h_leaf_is_sibling[k] = 1 where entry k is a sibling that was NOT queried; at most
@@ -364,7 +375,9 @@ int ms_gather_digests(ms_ctx* ctx, size_t ndigests, const void* d_digests, const
 /* The same for nseg digest arrays in ONE launch: segment s gathers counts[s] records of d_digests[s] (ndigests[s] records long) into
  * d_out[s]; h_indices holds the segments' index lists one after another.  The openings of a proof list leaves, siblings and nodes of
  * every committed tree (two trace trees + one per FRI layer: src/prover.rs:161-173, src/fri.rs:148-165): two dozen gathers of a few
- * records each, i.e. two dozen launch latencies -- the bindings collect them and call this once. */
+ * records each, i.e. two dozen launch latencies -- the bindings collect them and call this once.  The output of a segment must not overlap
+ * the digest array of ANY segment of the call, nor another segment's output (MS_ERR_INVALID, "... overlap ...", nothing enqueued);
+ * segments with counts[s] == 0 move nothing and are not looked at. */
 int ms_gather_digests_multi(ms_ctx* ctx, unsigned nseg, const void* const* d_digests, const size_t* ndigests, const uint64_t* h_indices,
                             const size_t* counts, void* const* d_out);
 

@@ -1224,11 +1224,18 @@ extern "C" int ms_deinterleave(ms_ctx* ctx, int field, size_t n_out, unsigned k,
     if (!fb) return fail(MS_ERR_UNSUPPORTED, "unknown field %d", field);
     if (k == 0 || k > (unsigned)msstage::MAXCOLS) return fail(MS_ERR_UNSUPPORTED, "1..%d columns", msstage::MAXCOLS);
     if (n_out == 0) return MS_OK;
+    // element j of column c comes from element j*k + c of d_in, which another lane reads: no column may lie over d_in or over another column
+    for (unsigned c = 0; c < k; c++) {
+        if (!d_out[c]) return fail(MS_ERR_INVALID, "null column %u", c);
+        if (ranges_overlap(d_out[c], n_out * fb, d_in, n_out * k * fb)) return fail(MS_ERR_INVALID, "ms_deinterleave: output column %u and d_in overlap", c);
+        for (unsigned f = 0; f < c; f++)
+            if (ranges_overlap(d_out[c], n_out * fb, d_out[f], n_out * fb)) return fail(MS_ERR_INVALID, "ms_deinterleave: output columns %u and %u overlap", f, c);
+    }
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     msscan::DeinterleaveParams P;
     memset(&P, 0, sizeof P);
-    for (unsigned c = 0; c < k; c++) { if (!d_out[c]) return fail(MS_ERR_INVALID, "null column %u", c); P.out[c] = (uint64_t*)d_out[c]; }
+    for (unsigned c = 0; c < k; c++) P.out[c] = (uint64_t*)d_out[c];
     P.in = (const uint64_t*)d_in; P.n_out = n_out; P.k = k; P.V = (unsigned)(fb / 8);
     const size_t total = n_out * k * P.V;
     ProfScope ps(ctx, "deinterleave", 16.0 * total);

@@ -377,6 +377,11 @@ extern "C" int ms_scan_affine(ms_ctx* ctx, int field, size_t n, const void* d_a,
     if (n == 0) return MS_OK;
     const size_t tile = (size_t)msscan::NT * scan_rows_per_lane(n, V);
     if ((n + tile - 1) / tile > 0xFFFFFFFFull) return fail(MS_ERR_UNSUPPORTED, "column too long");
+    // a workgroup reads its block's maps before it stores its rows, so d_out == d_a / d_b is the in-place form; any other overlap has one
+    // workgroup storing over rows another has not read yet.  d_a and d_b are only read: they may overlap each other in any way.
+    for (const void* src : {d_a, d_b})
+        if (src && src != d_out && ranges_overlap(d_out, n * V * 8, src, n * V * 8))
+            return fail(MS_ERR_INVALID, "ms_scan_affine: d_out and %s overlap (they must be disjoint or the same buffer)", src == d_a ? "d_a" : "d_b");
     MSCHK(canon_host(ctx, "ms_scan_affine", "h_init", field, h_init, 1));
     MSCHK(canon_col(ctx, "ms_scan_affine", "d_a", field, n, d_a));
     MSCHK(canon_col(ctx, "ms_scan_affine", "d_b", field, n, d_b));
@@ -410,6 +415,10 @@ extern "C" int ms_gather_rows(ms_ctx* ctx, int field, size_t nrows, const void* 
     if (ncols == 0 || ncols > (unsigned)msstage::MAXCOLS) return fail(MS_ERR_UNSUPPORTED, "1..%d columns", msstage::MAXCOLS);
     for (size_t p = 0; p < npos; p++) if (h_positions[p] >= nrows) return fail(MS_ERR_INVALID, "row %llu out of range", (unsigned long long)h_positions[p]);
     if (npos == 0) return MS_OK;
+    for (unsigned c = 0; c < ncols; c++) {      // lanes read any row of any column while others store: the output is disjoint from every column
+        if (!d_cols[c]) return fail(MS_ERR_INVALID, "null column %u", c);
+        if (ranges_overlap(d_out, npos * ncols * fb, d_cols[c], nrows * fb)) return fail(MS_ERR_INVALID, "ms_gather_rows: d_out and column %u overlap", c);
+    }
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     const void* d_pos = nullptr;
@@ -417,7 +426,7 @@ extern "C" int ms_gather_rows(ms_ctx* ctx, int field, size_t nrows, const void* 
     MSCHK(stage_view(ctx, h_positions, npos * 8, &d_pos, pooled));
     msscan::GatherRowsParams P;
     memset(&P, 0, sizeof P);
-    for (unsigned c = 0; c < ncols; c++) { if (!d_cols[c]) return fail(MS_ERR_INVALID, "null column %u", c); P.cols[c] = (const uint64_t*)d_cols[c]; }
+    for (unsigned c = 0; c < ncols; c++) P.cols[c] = (const uint64_t*)d_cols[c];
     P.pos = (const uint64_t*)d_pos; P.out = (uint64_t*)d_out; P.npos = npos; P.ncols = ncols; P.V = (unsigned)(fb / 8);
     const size_t total = npos * ncols * P.V;
     { ProfScope ps(ctx, "gather_rows", 16.0 * total);
@@ -463,6 +472,17 @@ extern "C" int ms_gather_digests_multi(ms_ctx* ctx, unsigned nseg, const void* c
     }
     if (total && !h_indices) return fail(MS_ERR_INVALID, "ms_gather_digests_multi: null indices");
     if (total == 0) return MS_OK;
+    // every output is disjoint from every segment's digest array and from the other outputs (empty segments move nothing: exempt)
+    for (unsigned s = 0; s < nseg; s++) {
+        if (!counts[s]) continue;
+        for (unsigned t = 0; t < nseg; t++) {
+            if (!counts[t]) continue;
+            if (ranges_overlap(d_out[s], 32 * counts[s], d_digests[t], 32 * ndigests[t]))
+                return fail(MS_ERR_INVALID, "ms_gather_digests_multi: the output of segment %u and the digests of segment %u overlap", s, t);
+            if (t < s && ranges_overlap(d_out[s], 32 * counts[s], d_out[t], 32 * counts[t]))
+                return fail(MS_ERR_INVALID, "ms_gather_digests_multi: the outputs of segments %u and %u overlap", t, s);
+        }
+    }
     std::vector<uint64_t> pairs(2 * total);
     size_t r = 0;
     for (unsigned s = 0; s < nseg; s++)
@@ -488,6 +508,7 @@ extern "C" int ms_gather_digests(ms_ctx* ctx, size_t ndigests, const void* d_dig
     if (!ctx || !d_digests || !d_out || (count && !h_indices)) return fail(MS_ERR_INVALID, "ms_gather_digests: null argument");
     for (size_t k = 0; k < count; k++) if (h_indices[k] >= ndigests) return fail(MS_ERR_INVALID, "digest %llu out of range", (unsigned long long)h_indices[k]);
     if (count == 0) return MS_OK;
+    if (ranges_overlap(d_out, 32 * count, d_digests, 32 * ndigests)) return fail(MS_ERR_INVALID, "ms_gather_digests: d_out and d_digests overlap");
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     const void* d_idx = nullptr;

@@ -2,7 +2,9 @@
 the sequential loop on Python integers (tests/ext_ref.py), word for word: lengths around the rows of a workgroup, offsets that wrap, 0 / 1 /
 8 terms per map, literal-1 coefficients, both signs, the three inits, the three masks, inclusive and exclusive output, 1 / 9 / 32 columns
 in a call, the three field pairs -- and the refusals, after which the sentinel-filled outputs are unchanged.  The kernels have ONE
-instantiation per field pair (4 rows per lane at every length), so there is no long-column case."""
+instantiation per field pair (4 rows per lane at every length), so the tile has no long-column case; the walk of the block aggregates has:
+ext_blocks is one workgroup per column whose lane t walks ceil(nblocks / 256) blocks, one block each up to 256 blocks = 256 * ROWS rows, two
+from the next row on.  test_block_walk_past_256_blocks runs both sides of that edge."""
 import ctypes
 import functools
 
@@ -98,6 +100,85 @@ def test_nine_designed_columns(kind, pair_name, n):
 @pytest.mark.parametrize("count", [1, 32])
 def test_batch_shapes(kind, pair_name, count):
     run_case(kind, pair_name, 1025, count)
+
+
+# ---- the block walk: 256 blocks (one per lane of ext_blocks) and 257 (two per lane, lane 128 holds the last one) ------------------------
+WALK_LENGTHS = [256 * B, 256 * B + 1]
+WALK_GUARD = np.array([0xA5A5A5A5A5A5A5A5, 0x5A5A5A5A5A5A5A5A] * 8, dtype=np.uint64)
+
+
+def walk_columns():
+    """three light columns in one call (gridDim.y = 3: every column has its own slice of agg and block_state); at most two terms per map,
+    the reference being a Python loop.  Base columns: 0, 1 values; 2 the mask of the first column (zero on row 0, non-zero on the last rows);
+    3 the mask of the third (non-zero on row 0, zero on the last rows)."""
+    return [
+        ExtColumn(1, [(+1, 0, None), (-1, None, 0, -1)], [], mask=("nonzero", 2)),                             # a masked running product of (chal0 - col0[i-1])
+        ExtColumn(0, [(+1, 1, None)], [(+1, 2, 1, +1)], inclusive=True),                                        # a running evaluation state * chal1 + chal2 * col1[i+1]
+        ExtColumn(("challenge", 3), [(+1, 4, 1)], [(+1, None, 0), (-1, 2, None)], mask=("zero", 3)),            # a challenge init under an if-zero mask
+    ]
+
+
+def walk_words(pair, vals, cubic=False):
+    """pair.base_words / pair.ext_words for a quarter of a million values: one list comprehension, the limbs cut from bytes"""
+    flat = [c for v in vals for c in v] if cubic else vals
+    R, p = pair.bf.R, pair.bf.p
+    raw = b"".join(((x * R) % p).to_bytes(pair.bf.nbytes, "little") for x in flat)
+    return np.frombuffer(raw, dtype=np.uint64).copy()
+
+
+@functools.lru_cache(maxsize=None)
+def walk_case(pair_name, n):
+    """(base columns, challenges, column records, base words, challenge words, expected words), computed once and shared by the backends"""
+    pair = PAIRS[pair_name]
+    rng = np.random.default_rng(77 + n)
+
+    def values():
+        if pair.bf.nlimbs == 1:
+            return rng.integers(0, pair.bf.p, size=n, dtype=np.uint64).tolist()
+        limbs = rng.integers(0, 1 << 64, size=(n, 4), dtype=np.uint64)
+        limbs[:, 3] >>= np.uint64(5)                      # below 2^251 < p
+        raw = limbs.tobytes()
+        return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
+    base = [values(), values()]
+    keep = rng.integers(0, 3, size=n)
+    keep[0], keep[-(B + 3):] = 0, 1                      # the first column: inactive on row 0, active on every row of the last block (and on the block before it)
+    base.append([v if k else 0 for v, k in zip(values(), keep)])
+    base.append([0 if k else v + 1 if v + 1 < pair.bf.p else 1 for v, k in zip(base[2], keep)])          # zero exactly where column 2 is not
+    chal = pair.random_ext(rng, NCHAL)
+    columns = walk_columns()
+    assert base[2][0] == 0 and base[3][0] != 0 and all(base[2][-B:]) and not any(base[3][-B:])
+    assert 0 in base[2][B:-B - 3] and 0 in base[3][B:-B - 3]                                                 # both masks switch in the middle blocks too
+    want = reference(pair, base, chal, columns)
+    for vals in (base[0][:40], base[2][-40:]):
+        assert np.array_equal(walk_words(pair, vals), pair.base_words(vals))
+    assert np.array_equal(walk_words(pair, want[1][-40:], pair.cubic), pair.ext_words(want[1][-40:]))
+    return base, chal, columns, [walk_words(pair, c) for c in base], pair.ext_words(chal), [walk_words(pair, w, pair.cubic) for w in want]
+
+
+# the simulator takes the longer length (two blocks per lane) only: it needs seconds for a quarter of a million rows of three columns
+@pytest.mark.parametrize("kind,n", [pytest.param(kind, n, id=f"{n}-{kind}", marks=[pytest.mark.gpu] if kind == "hip" else [])
+                                    for n in WALK_LENGTHS for kind in ("emu", "hip") if kind == "hip" or n == WALK_LENGTHS[1]])
+@pytest.mark.parametrize("pair_name", list(PAIRS))
+def test_block_walk_past_256_blocks(kind, pair_name, n):
+    """raw call: every output has guard words behind its last element; the base columns and the challenges are compared after it"""
+    pl, pair = backends.planner(kind), PAIRS[pair_name]
+    assert -(-n // B) == (256 if n == 256 * B else 257)
+    base, chal, columns, base_w, chal_w, want_w = walk_case(pair_name, n)
+    d_base = Matrix([GpuVec.from_numpy(pl, w, pair.base_field) for w in base_w])
+    d_chal = GpuVec.from_numpy(pl, chal_w, pair.ext_field)
+    call = Call(pl, pair, n, d_base, d_chal, columns)
+    V = {FP: 1, FQ3F: 3, F252F: 4}[pair.ext_field]
+    call.outs = [GpuVec.from_numpy(pl, np.concatenate([np.full(n * V, SENTINEL, dtype=np.uint64), WALK_GUARD]), FP) for _ in columns]
+    call.out_ptrs = [o.ptr for o in call.outs]
+    assert call() == 0, call.error()
+    for e, (o, w) in enumerate(zip(call.outs, want_w)):
+        got = o.to_numpy()
+        assert np.array_equal(got[n * V:], WALK_GUARD), (pair_name, n, e, "words behind the last element were written")
+        bad = np.nonzero(got[:n * V] != w)[0]
+        assert bad.size == 0, (pair_name, n, e, f"{bad.size} words differ, the first in row {int(bad[0]) // V}")
+    for c, w in zip(d_base.columns, base_w):
+        assert np.array_equal(c.to_numpy(), w)
+    assert np.array_equal(d_chal.to_numpy(), chal_w)
 
 
 @pytest.mark.parametrize("kind", KINDS)
