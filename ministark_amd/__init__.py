@@ -9,5 +9,5 @@ from .api import (GOLDILOCKS_FP, GOLDILOCKS_FQ3, STARK252_FP, GL_GENERATOR, GL_P
                   F252_P, F252_GENERATOR, f252_to_mont_limbs, f252_from_mont_limbs,
                   GpuRpo256ColumnMajor, GpuRpo256RowMajor, gen_rpo_merkle_tree, grind_proof_of_work,
                   scan_affine, running_product, Queries)
-from .extension import ExtColumn, build_extension_columns  # noqa: F401
+from .extension import ExtColumn, LogUpColumn, build_extension_columns, build_logup_columns  # noqa: F401
 from .debug import ConstraintViolation, ValidationReport, compile_constraints, validate_constraints  # noqa: F401

@@ -158,8 +158,13 @@ class Lib:
         ext_sigs = {
             "ms_build_extension_columns": (i, [vp, i, i, sz, c_void_pp, u, vp, u, vp, vp, u, c_void_pp]),
         }
+        # include/ministark_hip_logup.h: the LogUp lookup columns (running sums of fractions)
+        logup_sigs = {
+            "ms_build_logup_columns": (i, [vp, i, i, sz, c_void_pp, u, vp, u, vp, vp, vp, u, c_void_pp]),
+        }
         self.optional = {}
-        for name, (res, args) in list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items()):
+        for name, (res, args) in (list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items())
+                                  + list(logup_sigs.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -167,6 +172,7 @@ class Lib:
         self.transcript_sigs = transcript_sigs
         self.keccak_sigs = keccak_sigs
         self.ext_sigs = ext_sigs
+        self.logup_sigs = logup_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

@@ -12,6 +12,7 @@
 #include "ministark.hpp"
 #include "../../../include/ministark_hip_transcript.h"
 #include "../../../include/ministark_hip_ext.h"
+#include "../../../include/ministark_hip_logup.h"
 #include <stdint.h>
 // host arithmetic of the 252-bit field (points and offsets of its composer): the library's own fp252.h, kept inside ms:: so that its
 // Goldilocks namespace does not meet ms::gl in a program that says `using namespace ms`
@@ -124,6 +125,40 @@ inline Matrix<FqT> build_extension_columns(const Matrix<B>& base, const GpuVec<F
     for (size_t e = 0; e < columns.size(); e++) { out.columns.emplace_back(pl, n); outs.push_back(out.columns.back().ptr()); }
     check(ms_build_extension_columns(pl.ctx(), B::id, FqT::id, n, in.data(), (unsigned)in.size(), challenges ? challenges->ptr() : nullptr,
                                      challenges ? (unsigned)challenges->len() : 0u, recs.data(), terms.data(), (unsigned)columns.size(), outs.data()));
+    return out;
+}
+
+// LogUp lookup columns in one asynchronous call (ms_build_logup_columns): per column
+//     state = init;  for row i: out[i] = state;  if active(i): state = state + sum_f N_f(i) * inv(D_f(i)),   inv(0) = 0
+// N_f, D_f: sums of ExtTerms (an empty numerator is the literal 1; a denominator has at least one term)
+struct LogUpFraction { std::vector<ExtTerm> numerator, denominator; };
+struct LogUpColumn {
+    int init = MS_EXT_INIT_ZERO, init_chal = 0;                  // as ExtColumn's
+    std::vector<LogUpFraction> fractions;                        // none: the column holds its init everywhere
+    int mask = MS_EXT_ALWAYS, mask_col = 0;
+    bool inclusive = false;
+};
+template <class FqT, class B>
+inline Matrix<FqT> build_logup_columns(const Matrix<B>& base, const GpuVec<FqT>* challenges, const std::vector<LogUpColumn>& columns) {
+    Planner& pl = base.planner();
+    const size_t n = base.num_rows();
+    std::vector<ms_logup_column> recs;
+    std::vector<ms_logup_fraction> fracs;
+    std::vector<ms_ext_term> terms;
+    for (auto& c : columns) {
+        recs.push_back({c.init, c.init_chal, c.mask, c.mask_col, c.inclusive ? 1 : 0, (uint32_t)c.fractions.size(), 0, 0});
+        for (auto& f : c.fractions) {
+            fracs.push_back({(uint32_t)f.numerator.size(), (uint32_t)f.denominator.size()});
+            for (auto* list : {&f.numerator, &f.denominator}) for (auto& t : *list) terms.push_back({t.col, t.off, t.chal, t.sign});
+        }
+    }
+    std::vector<const void*> in;
+    for (auto& c : base.columns) in.push_back(c.ptr());
+    Matrix<FqT> out;
+    std::vector<void*> outs;
+    for (size_t e = 0; e < columns.size(); e++) { out.columns.emplace_back(pl, n); outs.push_back(out.columns.back().ptr()); }
+    check(ms_build_logup_columns(pl.ctx(), B::id, FqT::id, n, in.data(), (unsigned)in.size(), challenges ? challenges->ptr() : nullptr,
+                                 challenges ? (unsigned)challenges->len() : 0u, recs.data(), fracs.data(), terms.data(), (unsigned)columns.size(), outs.data()));
     return out;
 }
 

@@ -155,6 +155,44 @@ def permutation_air(n):
     return comp, ce, ncoeffs, 4, columns
 
 
+def lookup_trace(n, seed):
+    """A valid base trace of `lookup_air`: columns a0, a1, t0, t1, m as canonical integers.  Every looked-up pair (a0, a1)[i] is a row of the
+    table (t0, t1) and m[j] counts the rows that look table row j up.  Only the first half of the table is ever looked up, so the upper
+    half has m = 0 and -- n lookups into n / 2 rows -- some row has m >= 2."""
+    assert n >= 4
+    rng = np.random.default_rng(seed)
+    t = [[int(v) for v in rng.integers(0, GL_P, size=n, dtype=np.uint64)] for _ in range(2)]
+    idx = [int(v) for v in rng.integers(0, n // 2, size=n)]
+    m = [0] * n
+    for j in idx:
+        m[j] += 1
+    return [[t[0][j] for j in idx], [t[1][j] for j in idx]] + t + [m]
+
+
+def lookup_air_constraints(n):
+    """The two constraints of `lookup_air`, in its order: the boundary S = 0 at row 0, and the transition over the full zerofier X^n - 1."""
+    x = E.X()
+    cur, nxt, ch = (lambda k: E.Trace(k, 0)), (lambda k: E.Trace(k, 1)), E.Challenge
+    S = 5
+    dt, da = ch(0) - cur(2) - ch(1) * cur(3), ch(0) - cur(0) - ch(1) * cur(1)
+    return [cur(S) / (x - E.Constant(1)), ((nxt(S) - cur(S)) * dt * da - cur(4) * da + dt) / (x ** n - E.Constant(1))]
+
+
+def lookup_air(n):
+    """A small AIR with a logarithmic-derivative lookup (LogUp), valid on `lookup_trace`: every pair (a0, a1) is a row of the table (t0, t1),
+    which is looked up m times.  Base columns 0..4 = a0, a1, t0, t1, m; extension column 5 = S; challenges 0, 1 = alpha, beta:
+        S' = S + m / Dt - 1 / Da,      Dt = alpha - t0 - beta t1,      Da = alpha - a0 - beta a1
+    S = 0 at row 0, and the transition, cleared of its denominators, (S' - S) Dt Da - m Da + Dt = 0 on EVERY row (divided by X^n - 1):
+    Trace(S, 1) of the last row is S of row 0, so the wrap-around is the statement that the fractions sum to zero and there is no terminal
+    constraint.
+    -> (composition constraint, ce_blowup, number of composition coefficients, number of AIR challenges 2, the LogUpColumn record)."""
+    from .extension import LogUpColumn
+    comp, ce, ncoeffs = composition_constraint(n, lookup_air_constraints(n), num_air_challenges=2)
+    den = lambda c0, c1: [(+1, 0, None), (-1, None, c0), (-1, 1, c1)]
+    columns = [LogUpColumn(0, [([(+1, None, 4)], den(2, 3)), ([(-1, None, None)], den(0, 1))])]
+    return comp, ce, ncoeffs, 2, columns
+
+
 def additive_constraints(n_trace, ncols=8, ce_blowup=4):
     """A second, cheaper shape (the round-1/2 stand-in, kept as an extra case): additive transitions c_k = c_(k-2) + c_(k-1),
     each times (X - 3) / (X^n - 1) and (alpha_k X^3 + beta_k), evaluated on a constraint-evaluation domain of `ce_blowup` n points."""
@@ -429,8 +467,8 @@ def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, foldi
         grind -> reseed with the nonce                                              draw the query positions -> openings
     fq: the field every challenge is drawn from and the composition, DEEP and FRI phases work over: `field` (the default), or
     GOLDILOCKS_FQ3 over Goldilocks -- the reference's own choice for its Goldilocks AIRs, with or without an extension trace.
-    extension: a list of `extension.ExtColumn` -- the columns are built by ms_build_extension_columns from the challenges where the coin
-    drew them, and everything up to the extension commitment is enqueued without a host wait -- or a callable
+    extension: a list of `extension.ExtColumn` and `extension.LogUpColumn` records -- the columns are built by ms_build_extension_columns
+    and ms_build_logup_columns from the challenges where the coin drew them, and everything up to the extension commitment is enqueued without a host wait -- or a callable
     (base_trace, challenges GpuVec) -> Matrix of `fq` columns.  The composition constraint numbers the AIR's challenges first, then the
     composition coefficients (`composition_constraint(..., num_air_challenges=k)`); trace columns are numbered base | extension.
     The FRI commit phase is enqueued without a host wait: a layer's root is absorbed where the tree builder wrote it, alpha is drawn into
