@@ -48,6 +48,11 @@ class CoinState(ctypes.Structure):
                 ("bytes", ctypes.c_uint8 * 32)]
 
 
+class RpoCoinState(ctypes.Structure):
+    """`ms_rpo_coin_state` of include/ministark_hip_rpo_coin.h: the RPO-256 coin's sponge (Montgomery words) and its read position."""
+    _fields_ = [("s", ctypes.c_uint64 * 12), ("pos", ctypes.c_uint32), ("pad", ctypes.c_uint32 * 7)]
+
+
 class Lib:
     """Typed view of the C ABI in include/ministark_hip.h."""
 
@@ -162,9 +167,23 @@ class Lib:
         logup_sigs = {
             "ms_build_logup_columns": (i, [vp, i, i, sz, c_void_pp, u, vp, u, vp, vp, vp, u, c_void_pp]),
         }
+        # include/ministark_hip_rpo_coin.h: the RPO-256 public coin (each the twin of its ms_coin_* namesake, minus `hash`)
+        rpo_coin_sigs = {
+            "ms_rpo_coin_create": (i, [vp, vp, c_void_pp]),
+            "ms_rpo_coin_destroy": (i, [vp, vp]),
+            "ms_rpo_coin_read": (i, [vp, vp, vp]),
+            "ms_rpo_coin_write": (i, [vp, vp, vp]),
+            "ms_rpo_coin_reseed_digest": (i, [vp, vp, vp]),
+            "ms_rpo_coin_reseed_int": (i, [vp, vp, ctypes.c_uint64]),
+            "ms_rpo_coin_reseed_elements": (i, [vp, vp, i, vp, sz]),
+            "ms_rpo_coin_reseed_elements_host": (i, [vp, vp, i, vp, sz]),
+            "ms_rpo_coin_draw": (i, [vp, vp, i, sz, vp]),
+            "ms_rpo_coin_draw_queries": (i, [vp, vp, sz, sz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(sz)]),
+            "ms_rpo_coin_pow_grind": (i, [vp, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        }
         self.optional = {}
         for name, (res, args) in (list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items())
-                                  + list(logup_sigs.items())):
+                                  + list(logup_sigs.items()) + list(rpo_coin_sigs.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -173,6 +192,7 @@ class Lib:
         self.keccak_sigs = keccak_sigs
         self.ext_sigs = ext_sigs
         self.logup_sigs = logup_sigs
+        self.rpo_coin_sigs = rpo_coin_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

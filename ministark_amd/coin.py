@@ -1,15 +1,16 @@
 """`PublicCoinImpl<F, H>` (src/random.rs:61-141) as `ProverChannel` uses it (src/channel.rs:46-100, src/fri.rs:217-247), with its state
 in device memory: the ms_coin_* entry points of include/ministark_hip_transcript.h.  A commitment's root is absorbed where the tree builder left it
 (`MerkleTree.root_ptr()`), a drawn challenge stays on the device (`draw` returns a GpuVec that `api.apply_drp` hands to
-ms_fri_fold_dev), and none of the reseeds or draws waits for the device."""
+ms_fri_fold_dev), and none of the reseeds or draws waits for the device.  `RpoCoin` is the algebraic coin of
+include/ministark_hip_rpo_coin.h (ms_rpo_coin_*): the same methods over an RPO-256 sponge that absorbs and draws field elements."""
 import ctypes
 
 import numpy as np
 
 from . import _lib
-from .api import FIELD_WORDS, DeviceBytes, GpuVec
+from .api import FIELD_WORDS, GL_P, DeviceBytes, GpuVec, gl_from_mont, gl_to_mont
 
-HASH_IDS = {"sha256": 0, "blake2s": 1, "keccak256": 3, "sha3_256": 4}        # 2 is left for an RPO-256 coin
+HASH_IDS = {"sha256": 0, "blake2s": 1, "keccak256": 3, "sha3_256": 4}        # 2 stays unknown: the RPO-256 coin is RpoCoin, a family of its own
 
 
 class PublicCoin:
@@ -85,6 +86,105 @@ class PublicCoin:
     def close(self):
         if self.ptr and self.planner.handle:
             self.planner.lib.ms_coin_destroy(self.planner.handle, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rpo_seed(seed):
+    """The seed of an `RpoCoin`: four canonical integers, or 32 bytes read as four little-endian u64; every word below p."""
+    if isinstance(seed, (bytes, bytearray, memoryview)):
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("the coin's seed is 32 bytes (four little-endian u64) or four integers")
+        words = [int.from_bytes(seed[8 * k: 8 * k + 8], "little") for k in range(4)]
+    else:
+        words = [int(v) for v in seed]
+        if len(words) != 4:
+            raise ValueError("the coin's seed is 32 bytes (four little-endian u64) or four integers")
+    if any(not 0 <= w < GL_P for w in words):
+        raise ValueError("the words of an RPO-256 coin's seed are Goldilocks elements: below p")
+    return words
+
+
+class RpoCoin:
+    """The RPO-256 public coin (ms_rpo_coin_*): a 12-element sponge on the device, capacity s[0..4), rate s[4..12).  It has `PublicCoin`'s
+    methods, so `pipeline.prove` holds either.  seed: see `rpo_seed`.  The rules are in include/ministark_hip_rpo_coin.h."""
+
+    hash = "rpo256"
+
+    def __init__(self, planner, seed):
+        self.planner, self.ptr = planner, None
+        words = rpo_seed(seed)
+        h = ctypes.c_void_p()
+        buf = (ctypes.c_uint64 * 4)(*[gl_to_mont(w) for w in words])
+        planner.lib.check(planner.lib.ms_rpo_coin_create(planner.handle, buf, ctypes.byref(h)))
+        self.ptr = h.value
+
+    def _call(self, fn, *args):
+        self.planner.lib.check(fn(self.planner.handle, self.ptr, *args))
+
+    def reseed_digest(self, digest):
+        """Absorb four elements of device memory: a DeviceBytes (its first 32 bytes) or a device address, e.g. `tree.root_ptr()` of an
+        RPO-256 tree.  Asynchronous."""
+        self._call(self.planner.lib.ms_rpo_coin_reseed_digest, digest.ptr if isinstance(digest, DeviceBytes) else int(digest))
+
+    def reseed_int(self, value):
+        """Absorb a u64 as its two 32-bit halves (the proof-of-work nonce).  Asynchronous."""
+        self._call(self.planner.lib.ms_rpo_coin_reseed_int, int(value))
+
+    def reseed_elements(self, elems, field=None):
+        """Absorb field elements: a GpuVec, or numpy u64 Montgomery words of `field` (Fp or Fq3) elements on the host.  Asynchronous."""
+        L = self.planner.lib
+        if isinstance(elems, GpuVec):
+            self._call(L.ms_rpo_coin_reseed_elements, elems.field, elems.ptr, len(elems))
+            return
+        if field is None:
+            raise ValueError("reseed_elements: host elements need their field")
+        arr = np.ascontiguousarray(elems, dtype=np.uint64).ravel()
+        assert arr.size % FIELD_WORDS[field] == 0
+        self._call(L.ms_rpo_coin_reseed_elements_host, field, arr.ctypes.data, arr.size // FIELD_WORDS[field])
+
+    def draw(self, field, count=1):
+        """-> GpuVec of `count` elements of `field` (Fp or Fq3, Montgomery form), left on the device.  Asynchronous."""
+        out = GpuVec(self.planner, count, field)
+        self._call(self.planner.lib.ms_rpo_coin_draw, field, count, out.ptr)
+        return out
+
+    def draw_queries(self, max_n, domain_size):
+        """The distinct positions in ascending order; domain_size is a power of two up to 2^32.  Blocks."""
+        pos = np.empty(max(max_n, 1), dtype=np.uint64)
+        n = ctypes.c_size_t(0)
+        self._call(self.planner.lib.ms_rpo_coin_draw_queries, max_n, domain_size, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(n))
+        return [int(p) for p in pos[: n.value]]
+
+    def grind(self, bits, max_nonce=1 << 40):
+        """The smallest nonce >= 1 after whose `reseed_int` s[0] has its low `bits` bits zero; the coin is not reseeded.  Blocks."""
+        out = ctypes.c_uint64(0)
+        self._call(self.planner.lib.ms_rpo_coin_pow_grind, bits, max_nonce, ctypes.byref(out))
+        return out.value
+
+    def state(self):
+        """-> {"s": the 12 state elements as canonical integers, "pos": the next unread rate element (12: none)}.  Blocks."""
+        st = _lib.RpoCoinState()
+        self._call(self.planner.lib.ms_rpo_coin_read, ctypes.byref(st))
+        return {"s": [gl_from_mont(int(w)) for w in st.s], "pos": int(st.pos)}
+
+    def set_state(self, s, pos):
+        """ms_rpo_coin_write: replace the state (tests, checkpoints); s: 12 canonical integers, pos in 4..12."""
+        st = _lib.RpoCoinState()
+        for k, v in enumerate(s):
+            st.s[k] = gl_to_mont(int(v))
+        st.pos = pos
+        self._call(self.planner.lib.ms_rpo_coin_write, ctypes.byref(st))
+
+    def close(self):
+        if self.ptr and self.planner.handle:
+            self.planner.lib.ms_rpo_coin_destroy(self.planner.handle, self.ptr)
         self.ptr = None
 
     def __del__(self):

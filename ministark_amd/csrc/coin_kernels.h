@@ -1,6 +1,6 @@
 // The public coin of the Fiat-Shamir transcript, resident on the device: PublicCoinImpl<F, H> (src/random.rs:61-141) as
 // ProverChannel drives it (src/channel.rs:46-100, src/fri.rs:217-247), for H = SHA-256, BLAKE2s-256, Keccak-256 and SHA3-256
-// (the template parameter H is ms_coin_create's hash id: 0, 1, 3, 4; 2 is left for an RPO-256 coin).
+// (the template parameter H is ms_coin_create's hash id: 0, 1, 3, 4; 2 stays unknown -- the RPO-256 coin is a sponge, not a seed and a counter, and has a family of its own: rpo_coin_kernels.h, ms_rpo_coin_*).
 //
 // State (ms_coin_state of include/ministark_hip_transcript.h, 80 bytes in HBM): a 32-byte seed, a u64 counter and up to 32 unread bytes of the
 // last digest.  The rules, one device function each:

@@ -6,6 +6,7 @@
 //   Queries                           src/trace.rs:113-157
 //   grind_proof_of_work               src/random.rs:48-55
 //   PublicCoin                        src/random.rs:61-141, as ProverChannel uses it (src/channel.rs:46-100); state on the device
+//   RpoCoin                           the same calls on the algebraic RPO-256 coin (ministark_hip_rpo_coin.h)
 //   GpuRpo256ColumnMajor / RowMajor / gen_rpo_merkle_tree   gpu/src/plan.rs:32-174
 // Host values of Fq are canonical integers: FqVal{c0,c1,c2} (c1 = c2 = 0 when Fq = Fp).
 #pragma once
@@ -13,6 +14,7 @@
 #include "../../../include/ministark_hip_transcript.h"
 #include "../../../include/ministark_hip_ext.h"
 #include "../../../include/ministark_hip_logup.h"
+#include "../../../include/ministark_hip_rpo_coin.h"
 #include <stdint.h>
 // host arithmetic of the 252-bit field (points and offsets of its composer): the library's own fp252.h, kept inside ms:: so that its
 // Goldilocks namespace does not meet ms::gl in a program that says `using namespace ms`
@@ -244,7 +246,7 @@ inline uint64_t grind_proof_of_work(Planner& pl, const std::array<uint8_t, 32>& 
 }
 
 // PublicCoinImpl<F, H> (src/random.rs:61-141) with its state in device memory (ms_coin_*): H = SHA-256, or BLAKE2s-256 / Keccak-256 /
-// SHA3-256 for Hash::Blake2s / Keccak256 / Sha3_256 (ids 0, 1, 3, 4; an RPO-256 prover's coin is SHA-256, id 2 is left for an RPO-256 coin).
+// SHA3-256 for Hash::Blake2s / Keccak256 / Sha3_256 (ids 0, 1, 3, 4; an RPO-256 prover's coin is SHA-256 unless it asks for RpoCoin, below; id 2 stays unknown).
 // The reseeds and draw() enqueue and return; draw_queries, grind and state wait for the device.
 class PublicCoin {
 public:
@@ -270,6 +272,39 @@ public:
     }
     uint64_t grind(unsigned bits, uint64_t max_nonce = (uint64_t)1 << 40) { uint64_t nonce = 0; check(ms_coin_pow_grind(pl_->ctx(), coin_, bits, max_nonce, &nonce)); return nonce; }
     ms_coin_state state() const { ms_coin_state st; check(ms_coin_read(pl_->ctx(), coin_, &st)); return st; }
+private:
+    Planner* pl_;
+    void* coin_ = nullptr;
+};
+
+// The RPO-256 public coin (ms_rpo_coin_*, include/ministark_hip_rpo_coin.h): PublicCoin's methods over a 12-element sponge that absorbs and
+// draws Goldilocks elements (Fp or Fq3), for a prover whose verifier runs inside another proof.  seed: four canonical integers below p.
+// The reseeds and draw() enqueue and return; draw_queries, grind and state wait for the device.  state(): Montgomery words, as stored.
+class RpoCoin {
+public:
+    RpoCoin(Planner& pl, const std::array<uint64_t, 4>& seed) : pl_(&pl) {
+        uint64_t m[4];
+        for (int q = 0; q < 4; q++) { if (seed[q] >= gl::P) throw std::invalid_argument("RpoCoin: seed words are below p"); m[q] = gl::to_mont(seed[q]); }
+        check(ms_rpo_coin_create(pl.ctx(), m, &coin_));
+    }
+    ~RpoCoin() { if (coin_) ms_rpo_coin_destroy(pl_->ctx(), coin_); }
+    RpoCoin(const RpoCoin&) = delete; RpoCoin& operator=(const RpoCoin&) = delete;
+    void reseed_digest(const void* d_digest4) { check(ms_rpo_coin_reseed_digest(pl_->ctx(), coin_, d_digest4)); }   // e.g. the root_ptr() of an RPO-256 tree
+    void reseed_int(uint64_t value) { check(ms_rpo_coin_reseed_int(pl_->ctx(), coin_, value)); }
+    template <class F> void reseed_elements(const GpuVec<F>& elems, size_t count) { check(ms_rpo_coin_reseed_elements(pl_->ctx(), coin_, F::id, elems.ptr(), count)); }
+    template <class F> void reseed_elements(const GpuVec<F>& elems) { reseed_elements(elems, elems.len()); }
+    template <class F> void reseed_elements(const std::vector<uint64_t>& mont_words) {                            // host elements, Montgomery words
+        check(ms_rpo_coin_reseed_elements_host(pl_->ctx(), coin_, F::id, mont_words.data(), mont_words.size() / F::words));
+    }
+    template <class F> GpuVec<F> draw(size_t count = 1) { GpuVec<F> out(*pl_, count); check(ms_rpo_coin_draw(pl_->ctx(), coin_, F::id, count, out.ptr())); return out; }
+    std::vector<size_t> draw_queries(size_t max_n, size_t domain_size) {
+        std::vector<uint64_t> pos(max_n ? max_n : 1);
+        size_t n = 0;
+        check(ms_rpo_coin_draw_queries(pl_->ctx(), coin_, max_n, domain_size, pos.data(), &n));
+        return std::vector<size_t>(pos.begin(), pos.begin() + n);
+    }
+    uint64_t grind(unsigned bits, uint64_t max_nonce = (uint64_t)1 << 40) { uint64_t nonce = 0; check(ms_rpo_coin_pow_grind(pl_->ctx(), coin_, bits, max_nonce, &nonce)); return nonce; }
+    ms_rpo_coin_state state() const { ms_rpo_coin_state st; check(ms_rpo_coin_read(pl_->ctx(), coin_, &st)); return st; }
 private:
     Planner* pl_;
     void* coin_ = nullptr;

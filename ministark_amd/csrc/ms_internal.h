@@ -1,5 +1,5 @@
 // Internal declarations shared by the translation units of libministark_hip.so (ms_core / ms_ntt / ms_hash / ms_stage /
-// ms_eval / ms_deep / ms_comm / ms_coin .cpp): the context, the plan object, error plumbing, pooled scratch.  Not part of the C ABI.
+// ms_eval / ms_deep / ms_comm / ms_coin / ms_rpo_coin .cpp): the context, the plan object, error plumbing, pooled scratch.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -68,6 +68,7 @@ struct ms_ctx {
     size_t pool_bytes = 0, pool_cap = (size_t)96 << 30;
     std::map<void*, size_t> live;            // size of every block handed out by ms_alloc
     std::map<void*, int> coins;              // public coins created on this context (ms_coin.cpp): device state -> MS_HASH_*
+    std::map<void*, int> rpo_coins;          // RPO-256 coins (ms_rpo_coin.cpp): a registry of its own, so that neither family takes the other's handles
     // pinned staging ring for the small host arrays entry points take (query positions, digest indices): the copy to the
     // device is then truly asynchronous and the call does not drain the stream (stage_upload)
     char* stage = nullptr;

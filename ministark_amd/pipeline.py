@@ -456,7 +456,7 @@ def from_fq_words(fq, words):
 
 def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, folding=8, max_remainder_coeffs=64, grinding_bits=8,
           num_queries=32, hash="sha256", keep=False, ce_blowup=None, field=GOLDILOCKS_FP, trace_args=None, fq=None, num_air_challenges=0,
-          extension=None):
+          extension=None, coin=None):
     """The phases of `prove_phases` with every challenge drawn from the transcript: a device-resident `coin.PublicCoin` seeded with
     `seed32` (the digest of the public inputs, src/channel.rs:33-44) stands where `Draws` stood, in the reference's order
     (src/prover.rs:50-173, src/channel.rs:46-100, src/fri.rs:199-247):
@@ -475,12 +475,14 @@ def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, foldi
     device memory and the fold reads it there (ms_fri_fold_dev); roots and alphas are downloaded once, after the remainder.  The draws the
     host itself needs (challenges and composition coefficients for the evaluator, z, DEEP coefficients) are downloaded where they are needed,
     as the reference's are.  hints: canonical integers; H of the coin: BLAKE2s for a BLAKE2s prover, else SHA-256.
+    coin: None keeps that choice (`pow_hash(hash)`); "rpo256" runs the whole transcript, proof-of-work included, on the algebraic
+    `coin.RpoCoin` -- it needs hash="rpo256" and a Goldilocks `field` (fq Fp or Fq3), and takes seed32 as `coin.rpo_seed` does.
     Returns what prove_phases returns (without timings), plus the draws as canonical values (3-tuples when fq is Fq3): air_challenges,
     challenges (the composition coefficients), z, deep, fri_alphas, positions; `extension_root` when there is an extension trace.  keep=True
     adds the intermediate device objects of prove_phases, `ext_trace` / `ext_polys` / `ext_lde`, the coin, and `remainder_poly`: all n_rem
     coefficients of the remainder's interpolant, of which `remainder_coeffs` are the first n_rem / blowup (fri.rs:244 asserts the rest vanish)."""
     from .api import FIELD_WORDS, GOLDILOCKS_FQ3, GatherBatch, GpuVec
-    from .coin import PublicCoin
+    from .coin import PublicCoin, RpoCoin
     from .extension import build_extension_columns
     pl = planner
     if field not in (GOLDILOCKS_FP, STARK252_FP):
@@ -492,6 +494,10 @@ def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, foldi
         raise ValueError("prove: RPO-256 absorbs Goldilocks elements; the 252-bit field commits with sha256, blake2s, keccak256 or sha3_256")
     if trace.field != field:
         raise ValueError("prove: the trace is not over `field`")
+    if coin not in (None, "rpo256"):
+        raise ValueError('prove: coin is None (the byte coin of `hash`) or "rpo256"')
+    if coin == "rpo256" and (hash != "rpo256" or field != GOLDILOCKS_FP):
+        raise ValueError('prove: coin="rpo256" absorbs RPO-256 roots and Goldilocks elements: it needs hash="rpo256" and field=GOLDILOCKS_FP')
     h = field_generator(field)
     n_t = trace.num_rows()
     n_lde = n_t * blowup
@@ -500,7 +506,7 @@ def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, foldi
     n_ce = n_t * ce_blowup
     trace_dom, lde_dom, ce_dom = Radix2EvaluationDomain(n_t, 1, field), Radix2EvaluationDomain(n_lde, h, field), Radix2EvaluationDomain(n_ce, h, field)
     V = FIELD_WORDS[fq]
-    coin = PublicCoin(pl, seed32, pow_hash(hash))
+    coin = RpoCoin(pl, seed32) if coin == "rpo256" else PublicCoin(pl, seed32, pow_hash(hash))
     out = {}
 
     base_polys = trace.interpolate(trace_dom)                                  # prover.rs:50
