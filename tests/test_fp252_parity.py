@@ -155,10 +155,20 @@ def test_tiled_ntt_252_emu(log_n, offset, inverse):
 
 
 def test_tiled_ntt_252_three_passes_emu(monkeypatch):
+    """MS_NTT252_PASSES is read when a plan is BUILT and plans are cached per context: a context of its own, so that no 2^17 plan built
+    earlier in the process (two passes) is handed back, and the profile says that three passes ran."""
+    from ministark_amd import Planner
     monkeypatch.setenv("MS_NTT252_PASSES", "3")
-    pl = backends.planner("emu")
-    _ntt_case(pl, 17, 3, False, 1)
-    _ntt_case(pl, 17, 3, True, 2)
+    pl = Planner(0, backends.planner("emu").lib)
+    try:
+        pl.profile(True)
+        _ntt_case(pl, 17, 3, False, 1)
+        _ntt_case(pl, 17, 3, True, 2)
+        prof = pl.profile_read()
+        pl.profile(False)
+        assert {k: v["calls"] for k, v in prof.items()} == {"ntt252_pass1": 2, "ntt252_pass2": 2, "ntt252_pass3": 2}, prof
+    finally:
+        pl.close()
 
 
 def _lde_case(pl, log_n, log_b, offset, seed):
@@ -240,6 +250,13 @@ def test_fri_fold_252(kind, ff, offset):                # apply_drp, src/fri.rs:
     assert got == ofri.apply_drp(F.F252, None, evals, offset, alpha, ff)
 
 
+_M28 = (1 << 28) - 1
+# words at the boundaries of the nine 28-bit digits of csrc/fp252.h (taken modulo p where they are used: all canonical)
+DIGIT_EDGES_252 = [0, 1, 2, P - 1, P - 2, P - (1 << 28), (1 << 28) - 1, 1 << 28, (1 << 252) - 1 - (1 << 200), (1 << 251), (1 << 251) + 17 * (1 << 192),
+                   sum(_M28 << (28 * k) for k in range(0, 9, 2)) % P, sum(_M28 << (28 * k) for k in range(1, 9, 2)) % P, (1 << 224) - 1, 1 << 224,
+                   (1 << 192) * 17, P >> 1]
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_mul_edge_values_252(kind):
     # the product works on nine 28-bit digits with lazy 64-bit columns (csrc/fp252.h): digit boundaries, all-ones
@@ -247,9 +264,7 @@ def test_mul_edge_values_252(kind):
     pl = backends.planner(kind)
     n = 1 << (10 if kind == "emu" else 14)
     rng = np.random.default_rng(11)
-    M = (1 << 28) - 1
-    edge = [0, 1, 2, P - 1, P - 2, P - (1 << 28), (1 << 28) - 1, 1 << 28, (1 << 252) - 1 - (1 << 200), (1 << 251), (1 << 251) + 17 * (1 << 192),
-            sum(M << (28 * k) for k in range(0, 9, 2)) % P, sum(M << (28 * k) for k in range(1, 9, 2)) % P, (1 << 224) - 1, 1 << 224, (1 << 192) * 17, P >> 1]
+    M, edge = _M28, DIGIT_EDGES_252
     def draw():
         out = []
         for _ in range(n):
