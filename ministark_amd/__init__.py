@@ -9,5 +9,6 @@ from .api import (GOLDILOCKS_FP, GOLDILOCKS_FQ3, STARK252_FP, GL_GENERATOR, GL_P
                   F252_P, F252_GENERATOR, f252_to_mont_limbs, f252_from_mont_limbs,
                   GpuRpo256ColumnMajor, GpuRpo256RowMajor, gen_rpo_merkle_tree, grind_proof_of_work,
                   scan_affine, running_product, Queries)
-from .extension import ExtColumn, LogUpColumn, build_extension_columns, build_logup_columns  # noqa: F401
+from .extension import (ExtColumn, LogUpColumn, LookupMissing, LookupReport, LookupTuple, build_extension_columns, build_logup_columns,  # noqa: F401
+                        lookup_multiplicities)
 from .debug import ConstraintViolation, ValidationReport, compile_constraints, validate_constraints  # noqa: F401

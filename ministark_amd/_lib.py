@@ -53,6 +53,17 @@ class RpoCoinState(ctypes.Structure):
     _fields_ = [("s", ctypes.c_uint64 * 12), ("pos", ctypes.c_uint32), ("pad", ctypes.c_uint32 * 7)]
 
 
+class LookupReportRecord(ctypes.Structure):
+    """`ms_lookup_report` of include/ministark_hip_lookup.h: what ms_lookup_multiplicities found."""
+    _fields_ = [("missing", ctypes.c_uint64), ("first_missing_row", ctypes.c_uint64), ("first_missing_set", ctypes.c_uint32), ("pad", ctypes.c_uint32),
+                ("duplicate_table_rows", ctypes.c_uint64)]
+
+
+class LookupTupleRecord(ctypes.Structure):
+    """`ms_lookup_tuple` of include/ministark_hip_lookup.h."""
+    _fields_ = [("cols", ctypes.c_int32 * 4), ("mask", ctypes.c_int32), ("mask_col", ctypes.c_int32), ("pad0", ctypes.c_int32), ("pad1", ctypes.c_int32)]
+
+
 class Lib:
     """Typed view of the C ABI in include/ministark_hip.h."""
 
@@ -181,9 +192,13 @@ class Lib:
             "ms_rpo_coin_draw_queries": (i, [vp, vp, sz, sz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(sz)]),
             "ms_rpo_coin_pow_grind": (i, [vp, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         }
+        # include/ministark_hip_lookup.h: the multiplicity column of a LogUp lookup, counted on the device
+        lookup_sigs = {
+            "ms_lookup_multiplicities": (i, [vp, i, sz, c_void_pp, u, u, vp, vp, u, vp, vp]),
+        }
         self.optional = {}
         for name, (res, args) in (list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items())
-                                  + list(logup_sigs.items()) + list(rpo_coin_sigs.items())):
+                                  + list(logup_sigs.items()) + list(rpo_coin_sigs.items()) + list(lookup_sigs.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -193,6 +208,7 @@ class Lib:
         self.ext_sigs = ext_sigs
         self.logup_sigs = logup_sigs
         self.rpo_coin_sigs = rpo_coin_sigs
+        self.lookup_sigs = lookup_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

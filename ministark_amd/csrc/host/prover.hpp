@@ -3,6 +3,7 @@
 //   DeepPolyComposer                  src/composer.rs:17-188
 //   scan_affine / running_product     examples/brainfuck/trace.rs:108-289 (extension-column loops)
 //   ExtColumn / build_extension_columns   src/trace.rs build_extension_columns: every extension column in one call (ministark_hip_ext.h)
+//   LookupTuple / lookup_multiplicities   the m column of a LogUp lookup, counted on the device (ministark_hip_lookup.h)
 //   Queries                           src/trace.rs:113-157
 //   grind_proof_of_work               src/random.rs:48-55
 //   PublicCoin                        src/random.rs:61-141, as ProverChannel uses it (src/channel.rs:46-100); state on the device
@@ -15,6 +16,8 @@
 #include "../../../include/ministark_hip_ext.h"
 #include "../../../include/ministark_hip_logup.h"
 #include "../../../include/ministark_hip_rpo_coin.h"
+#include "../../../include/ministark_hip_lookup.h"
+#include <cstring>
 #include <stdint.h>
 // host arithmetic of the 252-bit field (points and offsets of its composer): the library's own fp252.h, kept inside ms:: so that its
 // Goldilocks namespace does not meet ms::gl in a program that says `using namespace ms`
@@ -162,6 +165,35 @@ inline Matrix<FqT> build_logup_columns(const Matrix<B>& base, const GpuVec<FqT>*
     check(ms_build_logup_columns(pl.ctx(), B::id, FqT::id, n, in.data(), (unsigned)in.size(), challenges ? challenges->ptr() : nullptr,
                                  challenges ? (unsigned)challenges->len() : 0u, recs.data(), fracs.data(), terms.data(), (unsigned)columns.size(), outs.data()));
     return out;
+}
+
+// The m column of a lookup in one asynchronous call (ms_lookup_multiplicities): m[j] = how many active rows of the `lookups` hold the tuple
+// of table row j (equal table rows: the first takes the credit).  cols: 1 .. MS_LOOKUP_MAX_WIDTH indices into the base matrix, the same
+// number in the table and in every set; mask as ExtColumn's.  m: n elements, possibly a column of `base` that no tuple and no mask names.
+struct LookupTuple { std::vector<int> cols; int mask = MS_EXT_ALWAYS, mask_col = 0; };
+struct LookupReport {
+    GpuVec<Fp> buf;                                              // the ms_lookup_report where the call wrote it
+    ms_lookup_report read() const { const std::vector<uint64_t> w = buf.to_host(); ms_lookup_report r; memcpy(&r, w.data(), sizeof r); return r; }   // a host wait
+};
+template <class B>
+inline LookupReport lookup_multiplicities(const Matrix<B>& base, const LookupTuple& table, const std::vector<LookupTuple>& lookups, GpuVec<B>& m) {
+    Planner& pl = base.planner();
+    auto record = [&](const LookupTuple& t) {
+        if (t.cols.empty() || t.cols.size() > (size_t)MS_LOOKUP_MAX_WIDTH || t.cols.size() != table.cols.size())
+            throw std::invalid_argument("lookup_multiplicities: a tuple has 1 .. 4 columns, as many as the table");
+        ms_lookup_tuple r = {{0, 0, 0, 0}, t.mask, t.mask_col, 0, 0};
+        for (size_t c = 0; c < t.cols.size(); c++) r.cols[c] = t.cols[c];
+        return r;
+    };
+    const ms_lookup_tuple trec = record(table);
+    std::vector<ms_lookup_tuple> lrecs;
+    for (auto& t : lookups) lrecs.push_back(record(t));
+    std::vector<const void*> in;
+    for (auto& c : base.columns) in.push_back(c.ptr());
+    LookupReport rep{GpuVec<Fp>(pl, sizeof(ms_lookup_report) / 8)};
+    check(ms_lookup_multiplicities(pl.ctx(), B::id, base.num_rows(), in.data(), (unsigned)in.size(), (unsigned)table.cols.size(), &trec,
+                                   lrecs.empty() ? nullptr : lrecs.data(), (unsigned)lrecs.size(), m.ptr(), rep.buf.ptr()));
+    return rep;
 }
 
 // `fold_positions` (src/fri.rs:615-622): strictly increasing positions -> their cosets, deduplicated

@@ -13,16 +13,24 @@ Logarithmic-derivative lookups (LogUp) are running sums of FRACTIONS of such lin
 
     state = init;  for row i: out[i] = state;  if active(i): state = state + sum_f N_f(i) * inv(D_f(i)),   inv(0) = 0
 
-`build_extension_columns` takes a list that mixes both kinds: one call of each, the columns returned in the order listed."""
+`build_extension_columns` takes a list that mixes both kinds: one call of each, the columns returned in the order listed.
+
+The m of a lookup -- how often each table row is looked up -- is a column of the BASE trace: `lookup_multiplicities` over
+ms_lookup_multiplicities (include/ministark_hip_lookup.h) counts it on the device, and its `LookupReport` names a looked-up tuple that the
+table does not hold."""
+import ctypes
+
 import numpy as np
 
-from .api import GpuVec, Matrix, _ptr_array
+from ._lib import LookupReportRecord, LookupTupleRecord
+from .api import FIELD_WORDS, GOLDILOCKS_FP, GpuVec, Matrix, _ptr_array, f252_from_mont_limbs, gl_from_mont
 
 MAX_TERMS, MAX_COLUMNS, NONE = 8, 32, -1
 ROWS_PER_WORKGROUP = 1024             # msext::ROWS (csrc/ext_kernels.h): the rows one workgroup scans; tests/test_ext_abi.py keeps the two equal
 _INIT = {0: 0, 1: 1}
 _MASK = {"nonzero": 1, "zero": 2}
 LOGUP_MAX_FRACTIONS, LOGUP_MAX_COLUMNS = 4, 32
+LOOKUP_MAX_WIDTH, LOOKUP_MAX_SETS = 4, 8
 
 
 class ExtColumn:
@@ -146,3 +154,103 @@ def build_logup_columns(planner, base, challenges, columns, fq, out=None):
     if columns:
         _build_logup(planner, cols, n, base_field, challenges, columns, fq, outs)
     return Matrix(outs)
+
+
+class LookupTuple:
+    """One tuple of base columns: the table's columns, or one set of looked-up columns.  cols: 1 .. 4 indices into the base matrix;
+    mask: None (every row is active), ("nonzero", m) or ("zero", m), as for ExtColumn."""
+
+    def __init__(self, cols, mask=None):
+        self.cols, self.mask = [int(c) for c in cols], mask
+        if not 1 <= len(self.cols) <= LOOKUP_MAX_WIDTH:
+            raise ValueError(f"LookupTuple: a tuple has 1 .. {LOOKUP_MAX_WIDTH} columns, not {len(self.cols)}")
+        if mask is not None and (len(mask) != 2 or mask[0] not in _MASK):
+            raise ValueError(f"LookupTuple: mask is None, ('nonzero', m) or ('zero', m), not {mask!r}")
+
+    def _record(self):
+        """the eight 32-bit words of ms_lookup_tuple: cols[4], mask, mask_col, pad0, pad1"""
+        mask = (0, 0) if self.mask is None else (_MASK[self.mask[0]], int(self.mask[1]))
+        return self.cols + [0] * (LOOKUP_MAX_WIDTH - len(self.cols)) + [mask[0], mask[1], 0, 0]
+
+
+class LookupMissing(LookupError):
+    """`LookupReport.check()`: a looked-up tuple is not a row of the table.  .set, .row, .values (canonical integers), .missing"""
+
+
+class LookupReport:
+    """What `lookup_multiplicities` found: the ms_lookup_report in device memory, downloaded (a host wait) when a field is first read.
+    .missing: looked-up rows whose tuple the table does not hold; .first_missing_set / .first_missing_row: the smallest (set, row) among
+    them (0, 0 when there is none); .duplicate_table_rows: active table rows equal to an earlier one (their m is 0)."""
+
+    def __init__(self, planner, buf, cols, lookups):
+        self.planner, self.buf, self._cols, self._lookups, self._rec = planner, buf, cols, lookups, None
+
+    def _read(self):
+        if self._rec is None:
+            rec = LookupReportRecord()
+            self.planner.lib.check(self.planner.lib.ms_download(self.planner.handle, ctypes.addressof(rec), self.buf.ptr, ctypes.sizeof(rec)))
+            self._rec = rec
+        return self._rec
+
+    missing = property(lambda self: int(self._read().missing))
+    first_missing_row = property(lambda self: int(self._read().first_missing_row))
+    first_missing_set = property(lambda self: int(self._read().first_missing_set))
+    duplicate_table_rows = property(lambda self: int(self._read().duplicate_table_rows))
+
+    def __bool__(self):
+        return self.missing == 0                 # true when every looked-up tuple was found
+
+    def __repr__(self):
+        return (f"LookupReport(missing={self.missing}, first_missing_set={self.first_missing_set}, first_missing_row={self.first_missing_row}, "
+                f"duplicate_table_rows={self.duplicate_table_rows})")
+
+    def first_missing_values(self):
+        """the canonical values of the first missing tuple (it downloads those elements, nothing else), or None"""
+        if not self.missing:
+            return None
+        row, L = self.first_missing_row, self.planner.lib
+        vals = []
+        for c in self._lookups[self.first_missing_set].cols:
+            col = self._cols[c]
+            V = FIELD_WORDS[col.field]
+            w = np.empty(V, dtype=np.uint64)
+            L.check(L.ms_download(self.planner.handle, w.ctypes.data, col.ptr + row * V * 8, V * 8))
+            vals.append(gl_from_mont(int(w[0])) if col.field == GOLDILOCKS_FP else f252_from_mont_limbs([int(x) for x in w]))
+        return vals
+
+    def check(self):
+        """raises LookupMissing, naming set, row and the tuple's values, when a looked-up tuple is not in the table"""
+        if self.missing:
+            s, row, vals = self.first_missing_set, self.first_missing_row, self.first_missing_values()
+            err = LookupMissing(f"lookup set {s}, row {row}: the tuple ({', '.join(str(v) for v in vals)}) in base columns {self._lookups[s].cols} "
+                                f"is not a row of the table; {self.missing} looked-up row(s) in all have no table row")
+            err.set, err.row, err.values, err.missing = s, row, vals, self.missing
+            raise err
+        return self
+
+
+def lookup_multiplicities(planner, base, table, lookups, out=None):
+    """-> (m, report): m[j] = how many active rows of the `lookups` (LookupTuple records of one width) hold the tuple of row j of `table`
+    (a LookupTuple), as elements of the base field; equal table rows: the first takes the credit.  base: a Matrix or a list of GpuVecs;
+    out: the GpuVec to fill -- it may be a column of `base` that no tuple and no mask names, the trace's own m column -- or None for a new
+    one.  report: a LookupReport.  Enqueues and returns: no host wait until the report is read."""
+    cols = base.columns if isinstance(base, Matrix) else list(base)
+    lookups = list(lookups)
+    if not cols:
+        raise ValueError("lookup_multiplicities: an empty base table")
+    n, field = len(cols[0]), cols[0].field
+    if any(len(c) != n or c.field != field for c in cols):
+        raise ValueError("lookup_multiplicities: base columns of different lengths or fields")
+    if any(len(t.cols) != len(table.cols) for t in lookups):
+        raise ValueError("lookup_multiplicities: every lookup set has as many columns as the table")
+    m = GpuVec(planner, n, field) if out is None else out
+    if len(m) != n or m.field != field:
+        raise ValueError("lookup_multiplicities: `out` is a column of the base field, as long as the base columns")
+    buf = GpuVec(planner, ctypes.sizeof(LookupReportRecord) // 8, GOLDILOCKS_FP)
+    trec = np.array(table._record(), dtype=np.int32)
+    lrec = np.array([t._record() for t in lookups], dtype=np.int32).reshape(-1, 8)
+    assert trec.nbytes == ctypes.sizeof(LookupTupleRecord)
+    L = planner.lib
+    L.check(L.ms_lookup_multiplicities(planner.handle, field, n, _ptr_array(cols), len(cols), len(table.cols), trec.ctypes.data,
+                                       lrec.ctypes.data if lrec.size else None, len(lookups), m.ptr, buf.ptr))
+    return m, LookupReport(planner, buf, cols, lookups)

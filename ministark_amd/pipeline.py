@@ -169,6 +169,20 @@ def lookup_trace(n, seed):
     return [[t[0][j] for j in idx], [t[1][j] for j in idx]] + t + [m]
 
 
+def lookup_trace_on_device(planner, n, seed, check=False):
+    """`lookup_trace(n, seed)` with its m column counted where the trace lies: the a and t columns are uploaded beside a zero m column and
+    ms_lookup_multiplicities (extension.lookup_multiplicities) fills that column in place -- no download, no host loop, no second upload.
+    -> the base trace as a Matrix of five Fp columns, equal to the uploaded `lookup_trace` in every word.  check: read the call's report
+    (a host wait) and raise LookupMissing if a looked-up pair is not a row of the table."""
+    from .extension import LookupTuple, lookup_multiplicities
+    cols = lookup_trace(n, seed)
+    trace = Matrix.from_numpy(planner, [to_mont_words(GOLDILOCKS_FP, c).ravel() for c in cols[:4]] + [np.zeros(n, dtype=np.uint64)], GOLDILOCKS_FP)
+    _, report = lookup_multiplicities(planner, trace, LookupTuple([2, 3]), [LookupTuple([0, 1])], out=trace.columns[4])
+    if check:
+        report.check()
+    return trace
+
+
 def lookup_air_constraints(n):
     """The two constraints of `lookup_air`, in its order: the boundary S = 0 at row 0, and the transition over the full zerofier X^n - 1."""
     x = E.X()
