@@ -64,6 +64,16 @@ class LookupTupleRecord(ctypes.Structure):
     _fields_ = [("cols", ctypes.c_int32 * 4), ("mask", ctypes.c_int32), ("mask_col", ctypes.c_int32), ("pad0", ctypes.c_int32), ("pad1", ctypes.c_int32)]
 
 
+class SortKeyRecord(ctypes.Structure):
+    """`ms_sort_key` of include/ministark_hip_sort.h."""
+    _fields_ = [("cols", ctypes.c_int32 * 4), ("mask", ctypes.c_int32), ("mask_col", ctypes.c_int32), ("pad0", ctypes.c_int32), ("pad1", ctypes.c_int32)]
+
+
+class SortReportRecord(ctypes.Structure):
+    """`ms_sort_report` of include/ministark_hip_sort.h: what ms_sort_rows found."""
+    _fields_ = [("active", ctypes.c_uint64), ("varying_bytes", ctypes.c_uint64)]
+
+
 class Lib:
     """Typed view of the C ABI in include/ministark_hip.h."""
 
@@ -196,9 +206,14 @@ class Lib:
         lookup_sigs = {
             "ms_lookup_multiplicities": (i, [vp, i, sz, c_void_pp, u, u, vp, vp, u, vp, vp]),
         }
+        # include/ministark_hip_sort.h: the permutation that sorts trace rows, and a gather by a device-resident index
+        sort_sigs = {
+            "ms_sort_rows": (i, [vp, i, sz, c_void_pp, u, u, vp, vp, vp]),
+            "ms_permute_columns": (i, [vp, i, sz, c_void_pp, c_void_pp, u, vp, sz]),
+        }
         self.optional = {}
         for name, (res, args) in (list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items())
-                                  + list(logup_sigs.items()) + list(rpo_coin_sigs.items()) + list(lookup_sigs.items())):
+                                  + list(logup_sigs.items()) + list(rpo_coin_sigs.items()) + list(lookup_sigs.items()) + list(sort_sigs.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -209,6 +224,7 @@ class Lib:
         self.logup_sigs = logup_sigs
         self.rpo_coin_sigs = rpo_coin_sigs
         self.lookup_sigs = lookup_sigs
+        self.sort_sigs = sort_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

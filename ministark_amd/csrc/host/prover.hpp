@@ -4,6 +4,7 @@
 //   scan_affine / running_product     examples/brainfuck/trace.rs:108-289 (extension-column loops)
 //   ExtColumn / build_extension_columns   src/trace.rs build_extension_columns: every extension column in one call (ministark_hip_ext.h)
 //   LookupTuple / lookup_multiplicities   the m column of a LogUp lookup, counted on the device (ministark_hip_lookup.h)
+//   SortKey / sort_rows / permute_columns   the rows of a table in key order (examples/brainfuck/vm.rs sort_by_key), on the device (ministark_hip_sort.h)
 //   Queries                           src/trace.rs:113-157
 //   grind_proof_of_work               src/random.rs:48-55
 //   PublicCoin                        src/random.rs:61-141, as ProverChannel uses it (src/channel.rs:46-100); state on the device
@@ -17,6 +18,7 @@
 #include "../../../include/ministark_hip_logup.h"
 #include "../../../include/ministark_hip_rpo_coin.h"
 #include "../../../include/ministark_hip_lookup.h"
+#include "../../../include/ministark_hip_sort.h"
 #include <cstring>
 #include <stdint.h>
 // host arithmetic of the 252-bit field (points and offsets of its composer): the library's own fp252.h, kept inside ms:: so that its
@@ -194,6 +196,51 @@ inline LookupReport lookup_multiplicities(const Matrix<B>& base, const LookupTup
     check(ms_lookup_multiplicities(pl.ctx(), B::id, base.num_rows(), in.data(), (unsigned)in.size(), (unsigned)table.cols.size(), &trec,
                                    lrecs.empty() ? nullptr : lrecs.data(), (unsigned)lrecs.size(), m.ptr(), rep.buf.ptr()));
     return rep;
+}
+
+// The permutation that sorts the first n rows of `base` (all of them by default) in one asynchronous call (ms_sort_rows): the active rows in
+// ascending order of the canonical values of cols[0] (most significant) .. cols[nkeys-1], rows of equal keys in their original order, then
+// the inactive rows in their original order.  cols: 1 .. MS_SORT_MAX_KEYS indices into the base matrix; mask as ExtColumn's.
+struct SortKey { std::vector<int> cols; int mask = MS_EXT_ALWAYS, mask_col = 0; };
+struct RowOrder {
+    GpuVec<Fp> index;                                            // n x uint32 where the call wrote them (two to a word)
+    GpuVec<Fp> report;                                           // the ms_sort_report
+    size_t n = 0;
+    std::vector<uint32_t> to_host() const {                      // a host wait
+        const std::vector<uint64_t> w = index.to_host();
+        std::vector<uint32_t> out(n);
+        if (n) memcpy(out.data(), w.data(), n * 4);
+        return out;
+    }
+    ms_sort_report read() const { const std::vector<uint64_t> w = report.to_host(); ms_sort_report r; memcpy(&r, w.data(), sizeof r); return r; }   // a host wait
+};
+template <class B>
+inline RowOrder sort_rows(const Matrix<B>& base, const SortKey& key, size_t n = (size_t)-1) {
+    Planner& pl = base.planner();
+    if (key.cols.empty() || key.cols.size() > (size_t)MS_SORT_MAX_KEYS) throw std::invalid_argument("sort_rows: a key has 1 .. 4 columns");
+    if (n == (size_t)-1) n = base.num_rows();
+    if (n > base.num_rows()) throw std::invalid_argument("sort_rows: more rows than the columns hold");
+    ms_sort_key rec = {{0, 0, 0, 0}, key.mask, key.mask_col, 0, 0};
+    for (size_t c = 0; c < key.cols.size(); c++) rec.cols[c] = key.cols[c];
+    std::vector<const void*> in;
+    for (auto& c : base.columns) in.push_back(c.ptr());
+    RowOrder out{GpuVec<Fp>(pl, (n + 1) / 2), GpuVec<Fp>(pl, sizeof(ms_sort_report) / 8), n};
+    check(ms_sort_rows(pl.ctx(), B::id, n, in.data(), (unsigned)in.size(), (unsigned)key.cols.size(), &rec, out.index.ptr(), out.report.ptr()));
+    return out;
+}
+// dst[c][i] = src[c][index[i]] for i < n_out (ms_permute_columns; a zero element where index[i] is no row of src): `order.n` entries by default
+template <class F>
+inline Matrix<F> permute_columns(const Matrix<F>& src, const RowOrder& order, size_t n_out = (size_t)-1) {
+    Planner& pl = src.planner();
+    if (n_out == (size_t)-1) n_out = order.n;
+    if (n_out > order.n) throw std::invalid_argument("permute_columns: more entries than the index holds");
+    Matrix<F> out;
+    std::vector<const void*> in;
+    std::vector<void*> to;
+    for (auto& c : src.columns) { in.push_back(c.ptr()); out.columns.emplace_back(pl, n_out); }
+    for (auto& c : out.columns) to.push_back(c.ptr());
+    check(ms_permute_columns(pl.ctx(), F::id, src.num_rows(), in.data(), to.data(), (unsigned)in.size(), order.index.ptr(), n_out));
+    return out;
 }
 
 // `fold_positions` (src/fri.rs:615-622): strictly increasing positions -> their cosets, deduplicated

@@ -17,13 +17,16 @@ Logarithmic-derivative lookups (LogUp) are running sums of FRACTIONS of such lin
 
 The m of a lookup -- how often each table row is looked up -- is a column of the BASE trace: `lookup_multiplicities` over
 ms_lookup_multiplicities (include/ministark_hip_lookup.h) counts it on the device, and its `LookupReport` names a looked-up tuple that the
-table does not hold."""
+table does not hold.
+
+Ordering rows -- a memory table by (address, cycle), the permuted columns of a permutation argument -- is `sort_rows` over ms_sort_rows and
+`permute_columns` over ms_permute_columns (include/ministark_hip_sort.h): the permutation is computed and applied in device memory."""
 import ctypes
 
 import numpy as np
 
-from ._lib import LookupReportRecord, LookupTupleRecord
-from .api import FIELD_WORDS, GOLDILOCKS_FP, GpuVec, Matrix, _ptr_array, f252_from_mont_limbs, gl_from_mont
+from ._lib import LookupReportRecord, LookupTupleRecord, SortKeyRecord, SortReportRecord
+from .api import FIELD_WORDS, GOLDILOCKS_FP, DeviceBytes, GpuVec, Matrix, _ptr_array, f252_from_mont_limbs, gl_from_mont
 
 MAX_TERMS, MAX_COLUMNS, NONE = 8, 32, -1
 ROWS_PER_WORKGROUP = 1024             # msext::ROWS (csrc/ext_kernels.h): the rows one workgroup scans; tests/test_ext_abi.py keeps the two equal
@@ -31,6 +34,7 @@ _INIT = {0: 0, 1: 1}
 _MASK = {"nonzero": 1, "zero": 2}
 LOGUP_MAX_FRACTIONS, LOGUP_MAX_COLUMNS = 4, 32
 LOOKUP_MAX_WIDTH, LOOKUP_MAX_SETS = 4, 8
+SORT_MAX_KEYS, PERMUTE_MAX_COLUMNS = 4, 128
 
 
 class ExtColumn:
@@ -254,3 +258,113 @@ def lookup_multiplicities(planner, base, table, lookups, out=None):
     L.check(L.ms_lookup_multiplicities(planner.handle, field, n, _ptr_array(cols), len(cols), len(table.cols), trec.ctypes.data,
                                        lrec.ctypes.data if lrec.size else None, len(lookups), m.ptr, buf.ptr))
     return m, LookupReport(planner, buf, cols, lookups)
+
+
+class SortKey:
+    """The key rows are sorted by: cols, 1 .. 4 indices into the base matrix, cols[0] the most significant; ascending, as canonical integers.
+    mask: None (every row is active), ("nonzero", m) or ("zero", m), as for ExtColumn: inactive rows follow the sorted ones, in their order."""
+
+    def __init__(self, cols, mask=None):
+        self.cols, self.mask = [int(c) for c in cols], mask
+        if not 1 <= len(self.cols) <= SORT_MAX_KEYS:
+            raise ValueError(f"SortKey: a key has 1 .. {SORT_MAX_KEYS} columns, not {len(self.cols)}")
+        if mask is not None and (len(mask) != 2 or mask[0] not in _MASK):
+            raise ValueError(f"SortKey: mask is None, ('nonzero', m) or ('zero', m), not {mask!r}")
+
+    def _record(self):
+        """the eight 32-bit words of ms_sort_key: cols[4], mask, mask_col, pad0, pad1"""
+        mask = (0, 0) if self.mask is None else (_MASK[self.mask[0]], int(self.mask[1]))
+        return self.cols + [0] * (SORT_MAX_KEYS - len(self.cols)) + [mask[0], mask[1], 0, 0]
+
+
+class DeviceIndex(DeviceBytes):
+    """n 32-bit row indices in device memory: the permutation `sort_rows` writes and `permute_columns` reads."""
+
+    def __init__(self, planner, n):
+        super().__init__(planner, 4 * n)
+        self.n = n
+
+    @classmethod
+    def from_numpy(cls, planner, arr):
+        arr = np.ascontiguousarray(arr, dtype=np.uint32).ravel()
+        v = cls(planner, arr.size)
+        if arr.size:
+            planner.lib.check(planner.lib.ms_upload(planner.handle, v.ptr, arr.ctypes.data, arr.nbytes))
+        return v
+
+    def to_numpy(self, n=None):
+        """the first n indices (default: all) on the host, as uint32 (a host wait)"""
+        return super().to_numpy(4 * (self.n if n is None else n)).view(np.uint32)
+
+    def __len__(self):
+        return self.n
+
+
+class SortReport:
+    """What `sort_rows` found: the ms_sort_report in device memory, downloaded (a host wait) when a field is first read.
+    .active: the rows the mask lets through (the sorted head of the permutation); .varying_bytes: the (component, byte) positions at which
+    two active rows differ -- the number of radix passes the call executed."""
+
+    def __init__(self, planner, buf):
+        self.planner, self.buf, self._rec = planner, buf, None
+
+    def _read(self):
+        if self._rec is None:
+            rec = SortReportRecord()
+            self.planner.lib.check(self.planner.lib.ms_download(self.planner.handle, ctypes.addressof(rec), self.buf.ptr, ctypes.sizeof(rec)))
+            self._rec = rec
+        return self._rec
+
+    active = property(lambda self: int(self._read().active))
+    varying_bytes = property(lambda self: int(self._read().varying_bytes))
+
+    def __repr__(self):
+        return f"SortReport(active={self.active}, varying_bytes={self.varying_bytes})"
+
+
+def _same_columns(what, cols):
+    if not cols:
+        raise ValueError(f"{what}: no columns")
+    n, field = len(cols[0]), cols[0].field
+    if any(len(c) != n or c.field != field for c in cols):
+        raise ValueError(f"{what}: columns of different lengths or fields")
+    return n, field
+
+
+def sort_rows(planner, base, key, n=None):
+    """-> (perm, report): perm, a DeviceIndex of n uint32, lists the active rows of `base` (a Matrix or a list of GpuVecs) in ascending order
+    of `key` (a SortKey) -- rows of equal keys in their original order -- and then the inactive rows in their original order.  n: sort the
+    first n rows only (default: all).  report: a SortReport.  Enqueues and returns: no host wait until the report or the index is read."""
+    cols = base.columns if isinstance(base, Matrix) else list(base)
+    rows, field = _same_columns("sort_rows", cols)
+    n = rows if n is None else int(n)
+    if not 0 <= n <= rows:
+        raise ValueError(f"sort_rows: {n} rows of columns that hold {rows}")
+    perm = DeviceIndex(planner, n)
+    buf = GpuVec(planner, ctypes.sizeof(SortReportRecord) // 8, GOLDILOCKS_FP)
+    rec = np.array(key._record(), dtype=np.int32)
+    assert rec.nbytes == ctypes.sizeof(SortKeyRecord)
+    L = planner.lib
+    L.check(L.ms_sort_rows(planner.handle, field, n, _ptr_array(cols), len(cols), len(key.cols), rec.ctypes.data, perm.ptr, buf.ptr))
+    return perm, SortReport(planner, buf)
+
+
+def permute_columns(planner, columns, index, n_out=None, out=None):
+    """-> a Matrix with out[c][i] = columns[c][index[i]] for i < n_out (a zero element where index[i] is not a row of `columns`).
+    columns: a Matrix or a list of GpuVecs of one field, at most 128; index: a DeviceIndex (or DeviceBytes holding uint32); n_out: how many
+    entries of it to use (default: all); out: GpuVecs of at least n_out elements to fill (their first n_out), or None for new ones."""
+    cols = columns.columns if isinstance(columns, Matrix) else list(columns)
+    n_src, field = _same_columns("permute_columns", cols)
+    held = index.nbytes // 4
+    n_out = held if n_out is None else int(n_out)
+    if not 0 <= n_out <= held:
+        raise ValueError(f"permute_columns: {n_out} entries of an index that holds {held}")
+    if out is None:
+        outs = [GpuVec(planner, n_out, field) for _ in cols]
+    else:
+        outs = out.columns if isinstance(out, Matrix) else list(out)
+        if len(outs) != len(cols) or any(len(o) < n_out or o.field != field for o in outs):
+            raise ValueError("permute_columns: `out` is one column per source column, of its field, of at least n_out elements")
+    L = planner.lib
+    L.check(L.ms_permute_columns(planner.handle, field, n_src, _ptr_array(cols), _ptr_array(outs), len(cols), index.ptr, n_out))
+    return Matrix(outs)

@@ -129,15 +129,45 @@ def permutation_trace(n, seed):
     return x + y
 
 
-def permutation_air(n):
-    """A small AIR with an extension trace, valid on `permutation_trace`: the rows (y0, y1) are a permutation of the rows (x0, x1), shown by
-    two running products over challenges drawn after the base commitment, plus a running evaluation of x0 (the three shapes of
-    examples/brainfuck/trace.rs:108-289).  Base columns 0..3 = x0, x1, y0, y1; extension columns 4..6 = P, Q, E; challenges 0..3 = alpha,
-    beta, gamma, delta:
-        P' = P (alpha - beta x0 - gamma x1)      Q' = Q (alpha - beta y0 - gamma y1)      E' = delta E + x0'
-    P = Q = 1 and E = 0 at row 0, P = Q at row n-1; the transitions hold on rows 0..n-2 (divided by (X^n - 1) / (X - g^(n-1))).
-    -> (composition constraint, ce_blowup 2, number of composition coefficients, number of AIR challenges 4, the ExtColumn records)."""
-    from .extension import ExtColumn
+SORTED_PERMUTATION_X0_RANGE = 16
+
+
+def sorted_permutation_trace(n, seed):
+    """A valid base trace of `permutation_air`, built on the host: x0 drawn from 0..15 (so rows tie on it), x1 at random, and the y rows of
+    0..n-2 the x rows of 0..n-2 sorted by (x0, x1) -- the order of a memory table; row n-1 is padding.  Canonical integers."""
+    rng = np.random.default_rng(seed)
+    x0 = [int(v) for v in rng.integers(0, SORTED_PERMUTATION_X0_RANGE, size=n)]
+    x1 = [int(v) for v in rng.integers(0, GL_P, size=n, dtype=np.uint64)]
+    pad = [int(v) for v in rng.integers(0, GL_P, size=2, dtype=np.uint64)]
+    order = sorted(range(n - 1), key=lambda i: (x0[i], x1[i]))
+    return [x0, x1, [x0[i] for i in order] + [pad[0]], [x1[i] for i in order] + [pad[1]]]
+
+
+def sorted_permutation_trace_on_device(planner, n, seed):
+    """`sorted_permutation_trace(n, seed)` with its y columns ordered where the trace lies: x0 and x1 are uploaded, ms_sort_rows
+    (extension.sort_rows) sorts rows 0..n-2 by (x0, x1), ms_permute_columns (extension.permute_columns) gathers them into y0 and y1, and the
+    padding row n-1 is written behind them -- no download, no host sort.  -> the base trace as a Matrix of four Fp columns, equal to the
+    uploaded `sorted_permutation_trace` in every word; `permutation_air(n)` is valid on it."""
+    from .api import GpuVec
+    from .extension import SortKey, permute_columns, sort_rows
+    rng = np.random.default_rng(seed)
+    x0 = rng.integers(0, SORTED_PERMUTATION_X0_RANGE, size=n)
+    x1 = rng.integers(0, GL_P, size=n, dtype=np.uint64)
+    pad = [int(v) for v in rng.integers(0, GL_P, size=2, dtype=np.uint64)]
+    x = Matrix.from_numpy(planner, [to_mont_words(GOLDILOCKS_FP, [int(v) for v in c]).ravel() for c in (x0, x1)], GOLDILOCKS_FP)
+    y = [GpuVec(planner, n, GOLDILOCKS_FP) for _ in range(2)]
+    perm, _ = sort_rows(planner, x, SortKey([0, 1]), n=n - 1)
+    permute_columns(planner, x, perm, out=y)
+    L = planner.lib
+    for col, v in zip(y, pad):
+        w = to_mont_words(GOLDILOCKS_FP, [v]).ravel()
+        L.check(L.ms_upload(planner.handle, col.ptr + 8 * (n - 1), w.ctypes.data, 8))
+    return Matrix(x.columns + y)
+
+
+def permutation_air_constraints(n):
+    """The seven constraints of `permutation_air`, in its order: the boundaries P = 1, Q = 1, E = 0 at row 0, the terminal P = Q at row
+    n-1, and the three transitions on rows 0..n-2."""
     x = E.X()
     dom = Radix2EvaluationDomain(n, 1, GOLDILOCKS_FP)
     last_x = pow(dom.group_gen, n - 1, dom.p)
@@ -149,7 +179,19 @@ def permutation_air(n):
           nxt(Q) - cur(Q) * (ch(0) - ch(1) * cur(2) - ch(2) * cur(3)),
           nxt(EV) - (ch(3) * cur(EV) + nxt(0))]
     zer = (x - E.Constant(last_x)) / (x ** n - E.Constant(1))
-    comp, ce, ncoeffs = composition_constraint(n, boundary + terminal + [t * zer for t in tr], num_air_challenges=4, min_ce_blowup=2)
+    return boundary + terminal + [t * zer for t in tr]
+
+
+def permutation_air(n):
+    """A small AIR with an extension trace, valid on `permutation_trace`: the rows (y0, y1) are a permutation of the rows (x0, x1), shown by
+    two running products over challenges drawn after the base commitment, plus a running evaluation of x0 (the three shapes of
+    examples/brainfuck/trace.rs:108-289).  Base columns 0..3 = x0, x1, y0, y1; extension columns 4..6 = P, Q, E; challenges 0..3 = alpha,
+    beta, gamma, delta:
+        P' = P (alpha - beta x0 - gamma x1)      Q' = Q (alpha - beta y0 - gamma y1)      E' = delta E + x0'
+    P = Q = 1 and E = 0 at row 0, P = Q at row n-1; the transitions hold on rows 0..n-2 (divided by (X^n - 1) / (X - g^(n-1))).
+    -> (composition constraint, ce_blowup 2, number of composition coefficients, number of AIR challenges 4, the ExtColumn records)."""
+    from .extension import ExtColumn
+    comp, ce, ncoeffs = composition_constraint(n, permutation_air_constraints(n), num_air_challenges=4, min_ce_blowup=2)
     product = lambda c0, c1: ExtColumn(1, [(+1, 0, None), (-1, 1, c0), (-1, 2, c1)], [])
     columns = [product(0, 1), product(2, 3), ExtColumn(0, [(+1, 3, None)], [(+1, None, 0, 1)])]
     return comp, ce, ncoeffs, 4, columns

@@ -25,6 +25,7 @@ pub mod sys_ext;
 pub mod sys_logup;
 pub mod sys_lookup;
 pub mod sys_rpo_coin;
+pub mod sys_sort;
 pub mod sys_transcript;
 pub mod utils;
 
