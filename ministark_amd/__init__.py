@@ -10,5 +10,6 @@ from .api import (GOLDILOCKS_FP, GOLDILOCKS_FQ3, STARK252_FP, GL_GENERATOR, GL_P
                   GpuRpo256ColumnMajor, GpuRpo256RowMajor, gen_rpo_merkle_tree, grind_proof_of_work,
                   scan_affine, running_product, Queries)
 from .extension import (ExtColumn, LogUpColumn, LookupMissing, LookupReport, LookupTuple, build_extension_columns, build_logup_columns,  # noqa: F401
-                        lookup_multiplicities, DeviceIndex, SortKey, SortReport, permute_columns, sort_rows)
+                        lookup_multiplicities, DeviceIndex, SortKey, SortReport, permute_columns, sort_rows,
+                        GapError, GapPlan, GapReport, GapSpec, gap_fill, gap_plan)
 from .debug import ConstraintViolation, ValidationReport, compile_constraints, validate_constraints  # noqa: F401

@@ -74,6 +74,22 @@ class SortReportRecord(ctypes.Structure):
     _fields_ = [("active", ctypes.c_uint64), ("varying_bytes", ctypes.c_uint64)]
 
 
+class GapSpecRecord(ctypes.Structure):
+    """`ms_gap_spec` of include/ministark_hip_gaps.h."""
+    _fields_ = [("group", ctypes.c_int32 * 3), ("ngroup", ctypes.c_int32), ("counter", ctypes.c_int32), ("mask", ctypes.c_int32), ("mask_col", ctypes.c_int32), ("pad0", ctypes.c_int32)]
+
+
+class GapReportRecord(ctypes.Structure):
+    """`ms_gap_report` of include/ministark_hip_gaps.h: what ms_gap_plan found."""
+    _fields_ = [("active", ctypes.c_uint64), ("rows_out", ctypes.c_uint64), ("gaps", ctypes.c_uint64), ("max_gap", ctypes.c_uint64), ("unordered", ctypes.c_uint64),
+                ("first_unordered", ctypes.c_uint64), ("saturated", ctypes.c_uint64), ("pad0", ctypes.c_uint64)]
+
+
+class GapColumnRecord(ctypes.Structure):
+    """`ms_gap_column` of include/ministark_hip_gaps.h."""
+    _fields_ = [("kind", ctypes.c_int32), ("src", ctypes.c_int32)]
+
+
 class Lib:
     """Typed view of the C ABI in include/ministark_hip.h."""
 
@@ -211,9 +227,14 @@ class Lib:
             "ms_sort_rows": (i, [vp, i, sz, c_void_pp, u, u, vp, vp, vp]),
             "ms_permute_columns": (i, [vp, i, sz, c_void_pp, c_void_pp, u, vp, sz]),
         }
+        # include/ministark_hip_gaps.h: a padded table derived where the trace lies -- select, fill clock gaps, pad
+        gap_sigs = {
+            "ms_gap_plan": (i, [vp, i, sz, c_void_pp, u, vp, vp, sz, vp, vp]),
+            "ms_gap_fill": (i, [vp, i, sz, c_void_pp, u, vp, sz, vp, vp, c_void_pp, u, sz]),
+        }
         self.optional = {}
         for name, (res, args) in (list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items())
-                                  + list(logup_sigs.items()) + list(rpo_coin_sigs.items()) + list(lookup_sigs.items()) + list(sort_sigs.items())):
+                                  + list(logup_sigs.items()) + list(rpo_coin_sigs.items()) + list(lookup_sigs.items()) + list(sort_sigs.items()) + list(gap_sigs.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -225,6 +246,7 @@ class Lib:
         self.rpo_coin_sigs = rpo_coin_sigs
         self.lookup_sigs = lookup_sigs
         self.sort_sigs = sort_sigs
+        self.gap_sigs = gap_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

@@ -5,6 +5,7 @@
 //   ExtColumn / build_extension_columns   src/trace.rs build_extension_columns: every extension column in one call (ministark_hip_ext.h)
 //   LookupTuple / lookup_multiplicities   the m column of a LogUp lookup, counted on the device (ministark_hip_lookup.h)
 //   SortKey / sort_rows / permute_columns   the rows of a table in key order (examples/brainfuck/vm.rs sort_by_key), on the device (ministark_hip_sort.h)
+//   GapSpec / gap_plan / gap_fill     derive_memory_rows and pad_*_rows (examples/brainfuck/vm.rs:282-380): select, fill clock gaps, pad, on the device (ministark_hip_gaps.h)
 //   Queries                           src/trace.rs:113-157
 //   grind_proof_of_work               src/random.rs:48-55
 //   PublicCoin                        src/random.rs:61-141, as ProverChannel uses it (src/channel.rs:46-100); state on the device
@@ -19,6 +20,7 @@
 #include "../../../include/ministark_hip_rpo_coin.h"
 #include "../../../include/ministark_hip_lookup.h"
 #include "../../../include/ministark_hip_sort.h"
+#include "../../../include/ministark_hip_gaps.h"
 #include <cstring>
 #include <stdint.h>
 // host arithmetic of the 252-bit field (points and offsets of its composer): the library's own fp252.h, kept inside ms:: so that its
@@ -240,6 +242,55 @@ inline Matrix<F> permute_columns(const Matrix<F>& src, const RowOrder& order, si
     for (auto& c : src.columns) { in.push_back(c.ptr()); out.columns.emplace_back(pl, n_out); }
     for (auto& c : out.columns) to.push_back(c.ptr());
     check(ms_permute_columns(pl.ctx(), F::id, src.num_rows(), in.data(), to.data(), (unsigned)in.size(), order.index.ptr(), n_out));
+    return out;
+}
+
+// A table whose row count differs from its source's, derived where the source lies (ms_gap_plan, ms_gap_fill): the rows the mask lets
+// through, a dummy row for every counter value missing between two consecutive rows that agree on the group columns, the last row repeated
+// up to n_out.  group: 0 .. MS_GAP_MAX_GROUP indices into the base matrix; counter: the clock column or -1 for no gaps; mask as ExtColumn's.
+struct GapSpec { std::vector<int> group; int counter = -1; int mask = MS_EXT_ALWAYS, mask_col = 0; };
+struct GapPlan {
+    GpuVec<Fp> start;                                            // (n + 1) x uint64: the prefix sums
+    GpuVec<Fp> report;                                           // the ms_gap_report
+    const RowOrder* order = nullptr;                             // the permutation the plan went through, or null; the caller keeps it alive
+    size_t n = 0;
+    std::vector<uint64_t> to_host() const { return start.to_host(); }   // a host wait
+    ms_gap_report read() const { const std::vector<uint64_t> w = report.to_host(); ms_gap_report r; memcpy(&r, w.data(), sizeof r); return r; }   // a host wait
+};
+template <class B>
+inline GapPlan gap_plan(const Matrix<B>& base, const GapSpec& spec, const RowOrder* order = nullptr, size_t n = (size_t)-1) {
+    Planner& pl = base.planner();
+    if (spec.group.size() > (size_t)MS_GAP_MAX_GROUP) throw std::invalid_argument("gap_plan: a group has 0 .. 3 columns");
+    const size_t held = order ? order->n : base.num_rows();
+    if (n == (size_t)-1) n = held;
+    if (n > held) throw std::invalid_argument("gap_plan: more positions than the index or the columns hold");
+    ms_gap_spec rec = {{0, 0, 0}, (int32_t)spec.group.size(), spec.counter, spec.mask, spec.mask_col, 0};
+    for (size_t c = 0; c < spec.group.size(); c++) rec.group[c] = spec.group[c];
+    std::vector<const void*> in;
+    for (auto& c : base.columns) in.push_back(c.ptr());
+    GapPlan out{GpuVec<Fp>(pl, n + 1), GpuVec<Fp>(pl, sizeof(ms_gap_report) / 8), order, n};
+    check(ms_gap_plan(pl.ctx(), B::id, base.num_rows(), in.data(), (unsigned)in.size(), &rec, order ? order->index.ptr() : nullptr, n, out.start.ptr(),
+                      out.report.ptr()));
+    return out;
+}
+// columns: (MS_GAP_COPY | MS_GAP_ZERO | MS_GAP_COUNTER | MS_GAP_FLAG, source column); n_out: by default the least power of two >= max(rows_out, 1),
+// which reads the report (the only host wait)
+template <class B>
+inline Matrix<B> gap_fill(const Matrix<B>& base, const GapPlan& plan, const std::vector<ms_gap_column>& columns, size_t n_out = (size_t)-1) {
+    Planner& pl = base.planner();
+    if (columns.empty() || columns.size() > (size_t)MS_GAP_MAX_COLUMNS) throw std::invalid_argument("gap_fill: 1 .. 128 columns");
+    if (n_out == (size_t)-1) {
+        const uint64_t rows = plan.read().rows_out;
+        for (n_out = 1; n_out < rows; n_out *= 2) {}
+    }
+    Matrix<B> out;
+    std::vector<const void*> in;
+    std::vector<void*> to;
+    for (auto& c : base.columns) in.push_back(c.ptr());
+    for (size_t c = 0; c < columns.size(); c++) out.columns.emplace_back(pl, n_out);
+    for (auto& c : out.columns) to.push_back(c.ptr());
+    check(ms_gap_fill(pl.ctx(), B::id, base.num_rows(), in.data(), (unsigned)in.size(), plan.order ? plan.order->index.ptr() : nullptr, plan.n, plan.start.ptr(),
+                      columns.data(), to.data(), (unsigned)columns.size(), n_out));
     return out;
 }
 

@@ -20,12 +20,16 @@ ms_lookup_multiplicities (include/ministark_hip_lookup.h) counts it on the devic
 table does not hold.
 
 Ordering rows -- a memory table by (address, cycle), the permuted columns of a permutation argument -- is `sort_rows` over ms_sort_rows and
-`permute_columns` over ms_permute_columns (include/ministark_hip_sort.h): the permutation is computed and applied in device memory."""
+`permute_columns` over ms_permute_columns (include/ministark_hip_sort.h): the permutation is computed and applied in device memory.
+
+A table whose row count differs from its source's -- the rows a mask selects, a dummy row for every clock cycle missing between two rows of
+an address, padding up to the trace length -- is `gap_plan` over ms_gap_plan and `gap_fill` over ms_gap_fill
+(include/ministark_hip_gaps.h): the device decides the row count and writes the rows."""
 import ctypes
 
 import numpy as np
 
-from ._lib import LookupReportRecord, LookupTupleRecord, SortKeyRecord, SortReportRecord
+from ._lib import GapColumnRecord, GapReportRecord, GapSpecRecord, LookupReportRecord, LookupTupleRecord, SortKeyRecord, SortReportRecord
 from .api import FIELD_WORDS, GOLDILOCKS_FP, DeviceBytes, GpuVec, Matrix, _ptr_array, f252_from_mont_limbs, gl_from_mont
 
 MAX_TERMS, MAX_COLUMNS, NONE = 8, 32, -1
@@ -367,4 +371,144 @@ def permute_columns(planner, columns, index, n_out=None, out=None):
             raise ValueError("permute_columns: `out` is one column per source column, of its field, of at least n_out elements")
     L = planner.lib
     L.check(L.ms_permute_columns(planner.handle, field, n_src, _ptr_array(cols), _ptr_array(outs), len(cols), index.ptr, n_out))
+    return Matrix(outs)
+
+
+GAP_MAX_GROUP, GAP_MAX_COLUMNS = 3, 128
+_GAP_KIND = {"copy": 0, "zero": 1, "counter": 2, "flag": 3}
+
+
+class GapSpec:
+    """Which rows a derived table takes and where rows are inserted (ms_gap_spec).  group: 0 .. 3 indices into the base matrix -- a gap is
+    only looked for between two consecutive rows that agree on them; counter: the index of the clock column, or None for no gaps (a plain
+    stable select, or plain padding); mask: None, ("nonzero", m) or ("zero", m), as for SortKey."""
+
+    def __init__(self, group=(), counter=None, mask=None):
+        self.group, self.counter, self.mask = [int(c) for c in group], None if counter is None else int(counter), mask
+        if len(self.group) > GAP_MAX_GROUP:
+            raise ValueError(f"GapSpec: a group has 0 .. {GAP_MAX_GROUP} columns, not {len(self.group)}")
+        if self.counter is not None and self.counter < 0:
+            raise ValueError(f"GapSpec: counter is a column index or None, not {counter!r}")
+        if mask is not None and (len(mask) != 2 or mask[0] not in _MASK):
+            raise ValueError(f"GapSpec: mask is None, ('nonzero', m) or ('zero', m), not {mask!r}")
+
+    def _record(self):
+        """the eight 32-bit words of ms_gap_spec: group[3], ngroup, counter, mask, mask_col, pad0"""
+        mask = (0, 0) if self.mask is None else (_MASK[self.mask[0]], int(self.mask[1]))
+        return self.group + [0] * (GAP_MAX_GROUP - len(self.group)) + [len(self.group), NONE if self.counter is None else self.counter, mask[0], mask[1], 0]
+
+
+class GapError(ValueError):
+    """`GapReport.check`: the counter does not ascend inside a group, or a gap was clipped."""
+
+
+class GapReport:
+    """What `gap_plan` found: the ms_gap_report in device memory, downloaded (a host wait) when a field is first read.
+    .active: the positions the mask lets through; .rows_out: the rows of the derived table before padding; .gaps: the positions a dummy row
+    follows; .max_gap: the longest run of dummy rows; .unordered / .first_unordered: positions whose counter does not ascend to the next
+    row of their group (first_unordered is None when there is none); .saturated: gaps clipped at 2^32."""
+
+    def __init__(self, planner, buf):
+        self.planner, self.buf, self._rec = planner, buf, None
+
+    def _read(self):
+        if self._rec is None:
+            rec = GapReportRecord()
+            self.planner.lib.check(self.planner.lib.ms_download(self.planner.handle, ctypes.addressof(rec), self.buf.ptr, ctypes.sizeof(rec)))
+            self._rec = rec
+        return self._rec
+
+    active = property(lambda self: int(self._read().active))
+    rows_out = property(lambda self: int(self._read().rows_out))
+    gaps = property(lambda self: int(self._read().gaps))
+    max_gap = property(lambda self: int(self._read().max_gap))
+    unordered = property(lambda self: int(self._read().unordered))
+    saturated = property(lambda self: int(self._read().saturated))
+
+    @property
+    def first_unordered(self):
+        v = int(self._read().first_unordered)
+        return None if v == (1 << 64) - 1 else v
+
+    def check(self):
+        """raises GapError when the derived table is not the one the host loop builds: -> self otherwise"""
+        if self.unordered:
+            raise GapError(f"gap_plan: at {self.unordered} positions the counter does not ascend to the next row of the group, the first at {self.first_unordered}")
+        if self.saturated:
+            raise GapError(f"gap_plan: {self.saturated} gaps are longer than 2^32 rows and were clipped")
+        return self
+
+    def __repr__(self):
+        return (f"GapReport(active={self.active}, rows_out={self.rows_out}, gaps={self.gaps}, max_gap={self.max_gap}, unordered={self.unordered}, "
+                f"first_unordered={self.first_unordered}, saturated={self.saturated})")
+
+
+class GapPlan:
+    """What `gap_plan` returns and `gap_fill` reads: .start, the n + 1 prefix sums in device memory (DeviceBytes, uint64); .report, a
+    GapReport; .perm, the index the plan went through (or None); .n, its positions; .n_src, the rows of the base columns."""
+
+    def __init__(self, start, report, perm, n, n_src, field):
+        self.start, self.report, self.perm, self.n, self.n_src, self.field = start, report, perm, n, n_src, field
+
+    def start_to_numpy(self):
+        """the n + 1 entries of start on the host, as uint64 (a host wait)"""
+        return self.start.to_numpy(8 * (self.n + 1)).view(np.uint64)
+
+
+def gap_plan(planner, base, spec, perm=None, n=None):
+    """-> a GapPlan: for each of the n positions of `perm` (a DeviceIndex such as `sort_rows` returns; None: the rows of `base` in their
+    order), how many rows of the derived table it gives -- none if the mask of `spec` (a GapSpec) does not hold, else 1 plus the clock
+    cycles missing up to the next position of the same group -- as prefix sums in device memory (ms_gap_plan).  n: the first n positions
+    only (default: all).  Enqueues and returns: no host wait until the report is read."""
+    cols = base.columns if isinstance(base, Matrix) else list(base)
+    rows, field = _same_columns("gap_plan", cols)
+    held = rows if perm is None else perm.nbytes // 4
+    n = held if n is None else int(n)
+    if not 0 <= n <= held:
+        raise ValueError(f"gap_plan: {n} positions of {'columns' if perm is None else 'an index'} that hold{'' if perm is None else 's'} {held}")
+    start = DeviceBytes(planner, 8 * (n + 1))
+    buf = GpuVec(planner, ctypes.sizeof(GapReportRecord) // 8, GOLDILOCKS_FP)
+    rec = np.array(spec._record(), dtype=np.int32)
+    assert rec.nbytes == ctypes.sizeof(GapSpecRecord)
+    L = planner.lib
+    L.check(L.ms_gap_plan(planner.handle, field, rows, _ptr_array(cols), len(cols), rec.ctypes.data, None if perm is None else perm.ptr, n, start.ptr, buf.ptr))
+    return GapPlan(start, GapReport(planner, buf), perm, n, rows, field)
+
+
+def gap_fill(planner, base, plan, columns, n_out=None, out=None):
+    """-> a Matrix of len(columns) columns of n_out rows: the derived table of `plan` (a GapPlan of the same `base`), padded (ms_gap_fill).
+    Output row j comes from the position s that covers it, k = j - start[s] rows after it; rows past the table continue its last row.
+    columns: ("copy", c): base column c at that position; ("zero", c): the same on the position's own row and zero on the k > 0 rows after
+    it; ("counter", c): the same plus k; ("flag", None): 0 on the own row, 1 after.  n_out: the rows to write; default: the least power of
+    two >= max(rows_out, 1), which reads the report (the only host wait).  out: GpuVecs of at least n_out elements to fill, or None."""
+    cols = base.columns if isinstance(base, Matrix) else list(base)
+    rows, field = _same_columns("gap_fill", cols)
+    if rows != plan.n_src or field != plan.field:
+        raise ValueError("gap_fill: the plan was made for other columns")
+    columns = list(columns)
+    if not 1 <= len(columns) <= GAP_MAX_COLUMNS:
+        raise ValueError(f"gap_fill: 1 .. {GAP_MAX_COLUMNS} columns, not {len(columns)}")
+    rec = []
+    for col in columns:
+        if len(col) != 2 or col[0] not in _GAP_KIND or (col[0] != "flag" and col[1] is None):
+            raise ValueError(f"gap_fill: a column is ('copy', c), ('zero', c), ('counter', c) or ('flag', None), not {col!r}")
+        rec += [_GAP_KIND[col[0]], 0 if col[0] == "flag" else int(col[1])]
+    if n_out is None:
+        n_out = 1
+        while n_out < plan.report.rows_out:
+            n_out *= 2
+    n_out = int(n_out)
+    if n_out < 0:
+        raise ValueError(f"gap_fill: {n_out} output rows")
+    if out is None:
+        outs = [GpuVec(planner, n_out, field) for _ in columns]
+    else:
+        outs = out.columns if isinstance(out, Matrix) else list(out)
+        if len(outs) != len(columns) or any(len(o) < n_out or o.field != field for o in outs):
+            raise ValueError("gap_fill: `out` is one column per record, of the base columns' field, of at least n_out elements")
+    rec = np.array(rec, dtype=np.int32)
+    assert rec.nbytes == len(columns) * ctypes.sizeof(GapColumnRecord)
+    L = planner.lib
+    L.check(L.ms_gap_fill(planner.handle, field, rows, _ptr_array(cols), len(cols), None if plan.perm is None else plan.perm.ptr, plan.n, plan.start.ptr,
+                          rec.ctypes.data, _ptr_array(outs), len(columns), n_out))
     return Matrix(outs)

@@ -249,6 +249,88 @@ def lookup_air(n):
     return comp, ce, ncoeffs, 2, columns
 
 
+def memory_processor_rows(steps, seed):
+    """The processor table of a small tape machine, as canonical integers: columns cycle, mp, mem_val, instr; `steps` executed rows and the
+    final state row, whose instr is 0.  Instructions 1..4, drawn at random: increment and decrement the cell under the pointer (mod p), move
+    the pointer right, move it left (at address 0 it stays).  mem_val is the cell's value BEFORE the instruction, as in
+    examples/brainfuck/vm.rs."""
+    rng = np.random.default_rng(seed)
+    instrs = [int(v) for v in rng.integers(1, 5, size=steps)] + [0]
+    mem, mp, rows = {}, 0, []
+    for cycle, ins in enumerate(instrs):
+        rows.append((cycle, mp, mem.get(mp, 0), ins))
+        if ins == 1:
+            mem[mp] = (mem.get(mp, 0) + 1) % GL_P
+        elif ins == 2:
+            mem[mp] = (mem.get(mp, 0) - 1) % GL_P
+        elif ins == 3:
+            mp += 1
+        elif ins == 4:
+            mp = max(mp - 1, 0)
+    return [[r[c] for r in rows] for c in range(4)]
+
+
+def memory_table_trace(steps, seed):
+    """The memory table of `memory_processor_rows(steps, seed)`, derived on the host as examples/brainfuck/vm.rs does (derive_memory_rows,
+    pad_memory_rows): the rows whose instr is not 0, sorted by (mp, cycle); a dummy row for every cycle missing between two rows of one
+    address; the last row repeated, its clock running on and dummy set, up to the least power of two.  -> columns cycle, mp, mem_val, dummy as
+    canonical integers."""
+    cycle, mp, val, ins = memory_processor_rows(steps, seed)
+    rows = sorted((mp[i], cycle[i], val[i]) for i in range(len(ins)) if ins[i] != 0)
+    out = []
+    for k, (a, c, v) in enumerate(rows):
+        out.append((c, a, v, 0))
+        if k + 1 < len(rows) and rows[k + 1][0] == a:
+            out += [(t, a, v, 1) for t in range(c + 1, rows[k + 1][1])]
+    n = 1
+    while n < len(out):
+        n *= 2
+    while len(out) < n:
+        c, a, v, _ = out[-1]
+        out.append(((c + 1) % GL_P, a, v, 1))
+    return [[r[c] for r in out] for c in range(4)]
+
+
+def memory_table_trace_on_device(planner, steps, seed, check=False):
+    """`memory_table_trace(steps, seed)` built where the processor table lies: its four columns are uploaded, ms_sort_rows
+    (extension.sort_rows) orders the rows whose instr is not 0 by (mp, cycle), ms_gap_plan (extension.gap_plan) goes through that permutation
+    with the same mask and counts, per row, the cycles missing up to the next row of its address, and ms_gap_fill (extension.gap_fill)
+    writes cycle (a counter), mp and mem_val (copies) and dummy (a flag), padded to the least power of two -- the table is never
+    downloaded; the one host wait reads the row count to size the result.  check: raise extension.GapError if a clock does not ascend.
+    -> a Matrix of four Fp columns, equal to the uploaded `memory_table_trace` in every word; `memory_air` is valid on it."""
+    from .extension import GapSpec, SortKey, gap_fill, gap_plan, sort_rows
+    proc = Matrix.from_numpy(planner, [to_mont_words(GOLDILOCKS_FP, c).ravel() for c in memory_processor_rows(steps, seed)], GOLDILOCKS_FP)
+    perm, _ = sort_rows(planner, proc, SortKey([1, 0], mask=("nonzero", 3)))
+    plan = gap_plan(planner, proc, GapSpec(group=[1], counter=0, mask=("nonzero", 3)), perm=perm)
+    if check:
+        plan.report.check()
+    return gap_fill(planner, proc, plan, [("counter", 0), ("copy", 1), ("copy", 2), ("flag", None)])
+
+
+def memory_air_constraints(n):
+    """The constraints of the reference's memory table (examples/brainfuck/constraints.rs:279-309) over columns 0..3 = cycle, mp, mem_val,
+    dummy, in its order: the boundaries cycle = mp = mem_val = 0 at row 0 and the six transitions on rows 0..n-2:
+        (mp' - mp - 1)(mp' - mp)      (mp' - mp) mem_val'      (dummy' - 1) dummy'      (mp' - mp) dummy      (mem_val' - mem_val) dummy
+        (mp' - mp - 1)(cycle' - cycle - 1)"""
+    x = E.X()
+    dom = Radix2EvaluationDomain(n, 1, GOLDILOCKS_FP)
+    last_x = pow(dom.group_gen, n - 1, dom.p)
+    cur, nxt, one = (lambda k: E.Trace(k, 0)), (lambda k: E.Trace(k, 1)), E.Constant(1)
+    CYCLE, MP, VAL, DUMMY = 0, 1, 2, 3
+    boundary = [cur(c) / (x - one) for c in (CYCLE, MP, VAL)]
+    step = nxt(MP) - cur(MP)
+    tr = [(step - one) * step, step * nxt(VAL), (nxt(DUMMY) - one) * nxt(DUMMY), step * cur(DUMMY), (nxt(VAL) - cur(VAL)) * cur(DUMMY),
+          (step - one) * (nxt(CYCLE) - cur(CYCLE) - one)]
+    zer = (x - E.Constant(last_x)) / (x ** n - one)
+    return boundary + [t * zer for t in tr]
+
+
+def memory_air(n):
+    """The AIR of `memory_air_constraints` as `prove` takes it, valid on `memory_table_trace`: -> (composition constraint, ce_blowup, number
+    of composition coefficients).  It has no extension trace and no challenges of its own."""
+    return composition_constraint(n, memory_air_constraints(n))
+
+
 def additive_constraints(n_trace, ncols=8, ce_blowup=4):
     """A second, cheaper shape (the round-1/2 stand-in, kept as an extra case): additive transitions c_k = c_(k-2) + c_(k-1),
     each times (X - 3) / (X^n - 1) and (alpha_k X^3 + beta_k), evaluated on a constraint-evaluation domain of `ce_blowup` n points."""

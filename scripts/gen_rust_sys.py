@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generate rust/gpu/src/hip/sys.rs -- the raw `extern "C"` bindings of the reference-side shim -- from
-include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h and sys_sort.rs from include/ministark_hip_sort.h.  tests/test_rust_shim.py re-runs the parser and
+include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h and sys_gaps.rs from include/ministark_hip_gaps.h.  tests/test_rust_shim.py re-runs the parser and
 checks the committed file against the header, which stands in for compiling it (no Rust toolchain in the image).
 
     python scripts/gen_rust_sys.py            # rewrite rust/gpu/src/hip/sys.rs
@@ -26,6 +26,8 @@ LOOKUP_HEADER = os.path.join(ROOT, "include", "ministark_hip_lookup.h")
 LOOKUP_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_lookup.rs")
 SORT_HEADER = os.path.join(ROOT, "include", "ministark_hip_sort.h")
 SORT_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_sort.rs")
+GAPS_HEADER = os.path.join(ROOT, "include", "ministark_hip_gaps.h")
+GAPS_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_gaps.rs")
 
 BASE = {"int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "long": "c_long", "size_t": "usize", "uint64_t": "u64",
         "uint32_t": "u32", "char": "c_char", "unsigned char": "u8", "void": "c_void", "ms_ctx": "ms_ctx", "ms_ntt_plan": "ms_ntt_plan", "ms_xchg_op": "ms_xchg_op", "ms_p2p_op": "ms_p2p_op", "ms_jit_stats": "ms_jit_stats"}
@@ -310,6 +312,33 @@ def sort_prototypes():
     return prototypes(text[text.index("#define MINISTARK_HIP_SORT_H"):])
 
 
+def render_gaps(protos):
+    """sys_gaps.rs: the entry points of include/ministark_hip_gaps.h (a padded table derived where the trace lies: select, fill clock gaps,
+    pad), on sys.rs's types; the mask kinds are sys_ext.rs's"""
+    lines = ["// GENERATED by scripts/gen_rust_sys.py from include/ministark_hip_gaps.h -- do not edit by hand.",
+             "// Raw bindings of the padded-table layer of libministark_hip.so (INTEGRATION.md section 3e); the MS_EXT_* mask kinds: sys_ext.rs.",
+             "#![allow(non_camel_case_types)]",
+             "use core::ffi::{c_int, c_uint, c_void};",
+             "use super::sys::ms_ctx;",
+             "",
+             "#[repr(C)] #[derive(Clone, Copy, Debug, Default)] pub struct ms_gap_spec { pub group: [i32; 3], pub ngroup: i32, pub counter: i32, pub mask: i32, pub mask_col: i32, pub pad0: i32 }",
+             "#[repr(C)] #[derive(Clone, Copy, Debug, Default)] pub struct ms_gap_report { pub active: u64, pub rows_out: u64, pub gaps: u64, pub max_gap: u64, pub unordered: u64, pub first_unordered: u64, pub saturated: u64, pub pad0: u64 }",
+             "#[repr(C)] #[derive(Clone, Copy, Debug, Default)] pub struct ms_gap_column { pub kind: i32, pub src: i32 }",
+             ] + [f"pub const {name}: c_int = {value};" for name, value in header_enums(GAPS_HEADER)] + [
+             "",
+             '#[link(name = "ministark_hip")]', 'extern "C" {']
+    for name, ret, plist in protos:
+        args = ", ".join(f"{(p + '_') if p in RUST_KEYWORDS else p}: {t}" for p, t in plist)
+        lines.append(f"    pub fn {name}({args})" + (f" -> {ret};" if ret else ";"))
+    lines += ["}", ""]
+    return "\n".join(lines)
+
+
+def gaps_prototypes():
+    text = open(GAPS_HEADER).read()
+    return prototypes(text[text.index("#define MINISTARK_HIP_GAPS_H"):])
+
+
 def main():
     protos = prototypes(open(HEADER).read())
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
@@ -344,6 +373,10 @@ def main():
     with open(SORT_OUT, "w") as f:
         f.write(render_sort(protos))
     print(f"{len(protos)} prototypes -> {SORT_OUT}")
+    protos = gaps_prototypes()
+    with open(GAPS_OUT, "w") as f:
+        f.write(render_gaps(protos))
+    print(f"{len(protos)} prototypes -> {GAPS_OUT}")
 
 
 if __name__ == "__main__":
