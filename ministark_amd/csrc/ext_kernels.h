@@ -11,6 +11,7 @@
 // All arithmetic is exact field arithmetic: results equal the sequential loop bit for bit.
 #pragma once
 #include "scan_kernels.h"
+#include "table_common.h"
 
 namespace msext {
 
@@ -28,7 +29,8 @@ static constexpr int PER = 4;                 // rows per lane at every length: 
 static constexpr int ROWS = NT * PER;
 static constexpr int MAXTERMS = 8, MAXEXT = 32;
 enum { INIT_ZERO = 0, INIT_ONE = 1, INIT_CHALLENGE = 2 };
-enum { MASK_ALWAYS = 0, MASK_IF_NONZERO = 1, MASK_IF_ZERO = 2 };
+using mstab::MASK_ALWAYS;
+using mstab::mask_holds;
 
 // resolved on the host: the column's address (nullptr: a constant term), the offset already reduced to [0, n)
 struct Term { const uint64_t* col; uint64_t off; int32_t chal; int32_t sign; };      // chal < 0: the literal 1
@@ -112,7 +114,7 @@ __device__ __forceinline__ Map<F> lane_maps(const Params& P, const Column& C, si
     #pragma unroll
     for (int j = 0; j < PER; j++) {
         bool active = e0 + (size_t)threadIdx.x * PER + j < P.n;
-        if (mask_kind != MASK_ALWAYS) active = active && (msstage::is_zero<typename B::T>(mk[j]) == (mask_kind == MASK_IF_ZERO));
+        if (mask_kind != MASK_ALWAYS) active = active && mask_holds<typename B::T>(mk[j], mask_kind);
         if (!active || !C.na) a[j] = F::one();
         if (!active || !C.nb) b[j] = f_zero<F>();
         const Map<F> mj = {a[j], b[j]};

@@ -15,25 +15,21 @@
 //                entries is staged in LDS and every thread searches there, a longer one (runs of inactive positions) is searched in global
 //                memory.  k = j - start[s] goes into Montgomery form with the field's own product.
 #pragma once
-#include "stage_kernels.h"
+#include "table_common.h"
 
 namespace msgap {
 
 static constexpr int NT = 256, ITEMS = 4, TILE = NT * ITEMS, SCAN_ROUND = NT, OUT_ITEMS = 4, OUT_TILE = NT * OUT_ITEMS, SLICE = 2048;
 static constexpr int MAXGROUP = 3, MAXCOLS = 128;
 static constexpr int COPY = 0, ZERO = 1, COUNTER = 2, FLAG = 3;
-static constexpr int MASK_ALWAYS = 0, MASK_IF_NONZERO = 1, MASK_IF_ZERO = 2;
 static constexpr uint64_t GAP_CAP = 1ull << 32;
 
-#ifdef MS_EMU
-static inline void add(uint64_t* p, uint64_t v) { *p += v; }
-static inline void amax(uint64_t* p, uint64_t v) { if (v > *p) *p = v; }
-static inline void amin(uint64_t* p, uint64_t v) { if (v < *p) *p = v; }
-#else
-static __device__ __forceinline__ void add(uint64_t* p, uint64_t v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
-static __device__ __forceinline__ void amax(uint64_t* p, uint64_t v) { atomicMax((unsigned long long*)p, (unsigned long long)v); }
-static __device__ __forceinline__ void amin(uint64_t* p, uint64_t v) { atomicMin((unsigned long long*)p, (unsigned long long)v); }
-#endif
+using mstab::mask_holds;
+using mstab::Canon;
+using mstab::add;
+using mstab::amax;
+using mstab::amin;
+using mstab::block_exclusive;
 
 struct Report { uint64_t active, rows_out, gaps, max_gap, unordered, first_unordered, saturated, pad0; };
 // the quantities a workgroup reduces, in the order of its LDS slots
@@ -51,25 +47,6 @@ struct PlanParams {
     uint32_t n, ntiles, ngroup;
     int32_t mask_kind;
 };
-
-// the canonical integer of element i of a column, least significant word first
-template <int V> struct Canon;
-template <> struct Canon<1> { static __device__ __forceinline__ void words(const uint64_t* col, size_t i, uint64_t* w) { w[0] = gl::from_mont(col[i]); } };
-template <> struct Canon<4> {
-    static __device__ __forceinline__ void words(const uint64_t* col, size_t i, uint64_t* w) {
-        const f252::E c = f252::from_mont(msstage::Fp252T::load(col, i));
-        w[0] = c.l[0]; w[1] = c.l[1]; w[2] = c.l[2]; w[3] = c.l[3];
-    }
-};
-
-template <int V>
-__device__ __forceinline__ bool holds(const PlanParams& P, size_t row) {
-    if (P.mask_kind == MASK_ALWAYS) return true;
-    uint64_t any = 0;
-    #pragma unroll
-    for (int l = 0; l < V; l++) any |= P.mask[row * V + l];
-    return (any == 0) == (P.mask_kind == MASK_IF_ZERO);
-}
 
 // b - a over V words: -> 0 when b <= a (unordered), else gap = min(b - a - 1, 2^32) and *clipped when b - a - 1 > 2^32
 template <int V>
@@ -107,7 +84,7 @@ __global__ void __launch_bounds__(NT) gap_count(PlanParams P) {
         if (j < n) {
             const size_t row = P.perm ? (size_t)P.perm[j] : j;
             if (row < P.n_src) {
-                act = holds<V>(P, row);
+                act = mask_holds<V>(P.mask, P.mask_kind, row);
                 if (act && P.counter) Canon<V>::words(P.counter, row, s_canon + (size_t)t * V);
             }
         }
@@ -180,33 +157,9 @@ __global__ void __launch_bounds__(NT) gap_count(PlanParams P) {
     }
 }
 
-// exclusive prefix over the NT 64-bit values of a workgroup (one per thread), through LDS; every thread calls it
-__device__ __forceinline__ uint64_t block_exclusive64(uint64_t v, uint64_t* s_a, uint64_t* s_b, uint64_t* sum) {
-    uint64_t *in = s_a, *out = s_b;
-    in[threadIdx.x] = v;
-    __syncthreads();
-    for (unsigned d = 1; d < (unsigned)NT; d <<= 1) {
-        out[threadIdx.x] = in[threadIdx.x] + (threadIdx.x >= d ? in[threadIdx.x - d] : 0ull);
-        __syncthreads();
-        uint64_t* t = in; in = out; out = t;
-    }
-    const uint64_t incl = in[threadIdx.x];
-    *sum = in[NT - 1];
-    __syncthreads();                                                           // the buffers are free again after this
-    return incl - v;
-}
-
 __global__ void __launch_bounds__(NT) gap_scan(PlanParams P) {
     __shared__ uint64_t s_a[NT], s_b[NT];
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < P.ntiles; base += SCAN_ROUND) {
-        const uint32_t t = base + threadIdx.x;
-        const uint64_t v = t < P.ntiles ? P.tile_sum[t] : 0ull;
-        uint64_t sum;
-        const uint64_t ex = block_exclusive64(v, s_a, s_b, &sum);
-        if (t < P.ntiles) P.tile_sum[t] = carry + ex;
-        carry += sum;
-    }
+    const uint64_t carry = mstab::prefix_in_rounds(P.tile_sum, P.ntiles, (unsigned)SCAN_ROUND, s_a, s_b);
     if (threadIdx.x == 0) { P.start[P.n] = carry; P.report->rows_out = carry; }
 }
 
@@ -217,7 +170,7 @@ __global__ void __launch_bounds__(NT) gap_starts(PlanParams P) {
     #pragma unroll
     for (int i = 0; i < ITEMS; i++) { c[i] = first + i < n ? P.start[first + i] : 0ull; mine += c[i]; }
     uint64_t sum;
-    uint64_t at = P.tile_sum[blockIdx.x] + block_exclusive64(mine, s_a, s_b, &sum);
+    uint64_t at = P.tile_sum[blockIdx.x] + block_exclusive(mine, (unsigned)NT, s_a, s_b, &sum);
     #pragma unroll
     for (int i = 0; i < ITEMS; i++) {
         if (first + i < n) P.start[first + i] = at;

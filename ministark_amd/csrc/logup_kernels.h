@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(NT) logup_increments(Params P) {
         #pragma unroll
         for (int j = 0; j < PER; j++) {
             active[j] = e0 + (size_t)threadIdx.x * PER + j < P.n;
-            if (mask_kind != msext::MASK_ALWAYS) active[j] = active[j] && (msstage::is_zero<typename B::T>(mk[j]) == (mask_kind == msext::MASK_IF_ZERO));
+            if (mask_kind != msext::MASK_ALWAYS) active[j] = active[j] && msext::mask_holds<typename B::T>(mk[j], mask_kind);
         }
     }
     T acc[PER];

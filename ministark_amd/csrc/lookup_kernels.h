@@ -15,33 +15,20 @@
 //                   tuple is missing -- counted, and atomicMin on (set << 32 | row).
 //                   Integer adds and mins commute: the counters and the report are the same on every run.
 //   lookup_finish   grid-stride: counter -> field element in Montgomery form -> d_m; lane 0 writes the report.
-// The simulator's header has no 32-bit atomics: mslk::cas / add / amin are plain read-modify-write under MS_EMU (the simulator runs lanes one
-// after another, so that is exact there) and the HIP atomics otherwise.
+// The mask predicate and cas / add / amin / peek are table_common.h's (plain read-modify-write under MS_EMU, the HIP atomics otherwise).
 #pragma once
-#include "stage_kernels.h"
+#include "table_common.h"
 
 namespace mslk {
 
 static constexpr int NT = 256, MAXW = 4, MAXSETS = 8;
 static constexpr uint32_t EMPTY = 0xFFFFFFFFu;
-static constexpr int MASK_ALWAYS = 0, MASK_IF_NONZERO = 1, MASK_IF_ZERO = 2;
 
-#ifdef MS_EMU
-static inline uint32_t cas(uint32_t* p, uint32_t expect, uint32_t v) { const uint32_t o = *p; if (o == expect) *p = v; return o; }
-static inline void amin(uint32_t* p, uint32_t v) { if (v < *p) *p = v; }
-static inline void amin(uint64_t* p, uint64_t v) { if (v < *p) *p = v; }
-static inline void add(uint32_t* p, uint32_t v) { *p += v; }
-static inline void add(uint64_t* p, uint64_t v) { *p += v; }
-static inline uint32_t peek(const uint32_t* p) { return *p; }
-#else
-static __device__ __forceinline__ uint32_t cas(uint32_t* p, uint32_t expect, uint32_t v) { return atomicCAS(p, expect, v); }
-static __device__ __forceinline__ void amin(uint32_t* p, uint32_t v) { atomicMin(p, v); }
-static __device__ __forceinline__ void amin(uint64_t* p, uint64_t v) { atomicMin((unsigned long long*)p, (unsigned long long)v); }
-static __device__ __forceinline__ void add(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
-static __device__ __forceinline__ void add(uint64_t* p, uint64_t v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
-// a slot while other lanes insert: a relaxed load that the compiler neither caches in a register nor serves from the CU's own cache
-static __device__ __forceinline__ uint32_t peek(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#endif
+using mstab::mask_holds;
+using mstab::cas;
+using mstab::amin;
+using mstab::add;
+using mstab::peek;
 
 struct Tuple {
     const uint64_t* cols[MAXW];               // cols[0 .. width)
@@ -64,15 +51,6 @@ struct Params {
 };
 
 template <int V> struct Key { uint64_t w[MAXW * V]; };
-
-template <int V>
-__device__ __forceinline__ bool active(const Tuple& T, size_t i) {
-    if (T.mask_kind == MASK_ALWAYS) return true;
-    uint64_t any = 0;
-    #pragma unroll
-    for (int l = 0; l < V; l++) any |= T.mask[i * V + l];
-    return (any == 0) == (T.mask_kind == MASK_IF_ZERO);
-}
 
 // the words of row i's tuple; components past the width are zero (in the key and in every key it is compared with)
 template <int V>
@@ -119,7 +97,7 @@ __global__ void __launch_bounds__(NT) lookup_build(Params P) {
     const unsigned width = P.width;
     uint64_t dups = 0;
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < P.n; i += (size_t)gridDim.x * NT) {
-        if (!active<V>(T, i)) continue;
+        if (!mask_holds<V>(T.mask, T.mask_kind, i)) continue;
         const Key<V> k = load_key<V>(T, width, i);
         uint32_t s = hash_key<V>(k, width) & P.capmask;
         for (;;) {
@@ -167,7 +145,7 @@ __global__ void __launch_bounds__(NT) lookup_count(Params P) {
     uint64_t missing = 0, first = ~0ull;
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < P.n; i += (size_t)gridDim.x * NT) {
         uint32_t found = EMPTY;
-        if (active<V>(L, i)) {
+        if (mask_holds<V>(L.mask, L.mask_kind, i)) {
             const Key<V> k = load_key<V>(L, width, i);
             uint32_t s = hash_key<V>(k, width) & P.capmask;
             for (;;) {

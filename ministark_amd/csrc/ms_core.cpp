@@ -1,5 +1,6 @@
 // Context, errors, pooled device memory, per-launch profiling (include/ministark_hip.h "runtime" / "memory").
 #include "ms_internal.h"
+#include "../../include/ministark_hip_ext.h"
 
 // ---------------------------------------------------------------------------------------
 // errors
@@ -28,6 +29,25 @@ int field_words(int field, unsigned* V) {
     if (field == MS_GOLDILOCKS_FQ3) { *V = 3; return MS_OK; }
     if (field == MS_STARK252_FP) { *V = 4; return MS_OK; }
     return fail(MS_ERR_INVALID, "unknown field id %d", field);
+}
+
+// the base-column table of a trace-table entry point (ms_internal.h)
+int BaseColumns::null_check() const {
+    for (unsigned c = 0; c < nbase; c++) if (!d_base[c]) return fail(MS_ERR_INVALID, "%s: null base column %u", me, c);
+    return MS_OK;
+}
+int BaseColumns::col(int index, const char* what, const uint64_t** ptr) {
+    if (index < 0 || (unsigned)index >= nbase) return fail(MS_ERR_INVALID, "%s: %scolumn %d out of range (%u)", me, what, index, nbase);
+    *ptr = (const uint64_t*)d_base[index];
+    if (std::find(used.begin(), used.end(), (unsigned)index) == used.end()) used.push_back((unsigned)index);
+    return MS_OK;
+}
+int BaseColumns::mask(int kind, int mask_col, const char* who, const uint64_t** ptr) {
+    if (kind < MS_EXT_ALWAYS || kind > MS_EXT_IF_ZERO) return fail(MS_ERR_INVALID, "%s: %sunknown mask kind %d", me, who, kind);
+    *ptr = nullptr;
+    if (kind == MS_EXT_ALWAYS) return MS_OK;
+    const std::string what = std::string(who) + "mask ";
+    return col(mask_col, what.c_str(), ptr);
 }
 
 // ---------------------------------------------------------------------------------------

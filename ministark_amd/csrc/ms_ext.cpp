@@ -1,11 +1,14 @@
 // Extension columns between the two trace commitments (Trace::build_extension_columns, src/trace.rs;
 // examples/brainfuck/trace.rs:108-289): include/ministark_hip_ext.h.
-#include "ms_internal.h"
-#include "../../include/ministark_hip_ext.h"
-#include "ext_kernels.h"
+#include "ext_args.h"
 
 static_assert(msext::MAXTERMS == (int)MS_EXT_MAX_TERMS && msext::MAXEXT == (int)MS_EXT_MAX_COLUMNS, "ext_kernels.h and the header disagree");
-static_assert((int)msext::INIT_CHALLENGE == (int)MS_EXT_INIT_CHALLENGE && (int)msext::MASK_IF_ZERO == (int)MS_EXT_IF_ZERO, "ext_kernels.h and the header disagree");
+static_assert((int)msext::INIT_ZERO == (int)MS_EXT_INIT_ZERO && (int)msext::INIT_ONE == (int)MS_EXT_INIT_ONE && (int)msext::INIT_CHALLENGE == (int)MS_EXT_INIT_CHALLENGE,
+              "ext_kernels.h and the header disagree");
+// the one place that ties the mask kinds of every trace-table kernel (table_common.h) to the header's: ms_logup / ms_lookup / ms_sort / ms_gaps
+// .cpp take MS_EXT_* from the same header and hand the value through
+static_assert(mstab::MASK_ALWAYS == (int)MS_EXT_ALWAYS && mstab::MASK_IF_NONZERO == (int)MS_EXT_IF_NONZERO && mstab::MASK_IF_ZERO == (int)MS_EXT_IF_ZERO,
+              "table_common.h and the extension header disagree");
 
 template <class F, class B>
 static void ext_launch(ms_ctx* ctx, const msext::Params& P, unsigned next, double term_bytes) {
@@ -36,7 +39,8 @@ extern "C" int ms_build_extension_columns(ms_ctx* ctx, int base_field, int ext_f
         nterms += hc[e].na + hc[e].nb;
     }
     if (nterms && !ht) return fail(MS_ERR_INVALID, "%s: null argument", me);
-    for (unsigned c = 0; c < nbase; c++) if (!d_base[c]) return fail(MS_ERR_INVALID, "%s: null base column %u", me, c);
+    BaseColumns R(me, d_base, nbase);
+    MSCHK(R.null_check());
     std::vector<msext::Column> cols(next);
     size_t at = 0;
     double term_bytes = 0;
@@ -44,41 +48,15 @@ extern "C" int ms_build_extension_columns(ms_ctx* ctx, int base_field, int ext_f
         const ms_ext_column& H = hc[e];
         msext::Column& C = cols[e];
         memset(&C, 0, sizeof C);
-        if (!d_out[e]) return fail(MS_ERR_INVALID, "%s: null output column %u", me, e);
-        if (H.init < MS_EXT_INIT_ZERO || H.init > MS_EXT_INIT_CHALLENGE) return fail(MS_ERR_INVALID, "%s: column %u: unknown init kind %d", me, e, H.init);
-        if (H.init == MS_EXT_INIT_CHALLENGE && (H.init_chal < 0 || (unsigned)H.init_chal >= nchallenges))
-            return fail(MS_ERR_INVALID, "%s: column %u: init challenge %d out of range (%u)", me, e, H.init_chal, nchallenges);
-        if (H.mask < MS_EXT_ALWAYS || H.mask > MS_EXT_IF_ZERO) return fail(MS_ERR_INVALID, "%s: column %u: unknown mask kind %d", me, e, H.mask);
-        if (H.mask != MS_EXT_ALWAYS && (H.mask_col < 0 || (unsigned)H.mask_col >= nbase))
-            return fail(MS_ERR_INVALID, "%s: column %u: mask column %d out of range (%u)", me, e, H.mask_col, nbase);
-        C.out = (uint64_t*)d_out[e];
-        C.mask = H.mask != MS_EXT_ALWAYS ? (const uint64_t*)d_base[H.mask_col] : nullptr;
+        MSCHK(msextargs::column_header(R, e, H, nchallenges, d_out[e], n, VB, &C, &term_bytes));
         C.na = H.na; C.nb = H.nb;
-        C.mask_kind = H.mask; C.init_kind = H.init; C.init_chal = H.init_chal; C.inclusive = H.inclusive != 0;
-        if (H.mask != MS_EXT_ALWAYS) term_bytes += 8.0 * n * VB;
-        for (unsigned k = 0; k < H.na + H.nb; k++, at++) {
-            const ms_ext_term& T = ht[at];
-            msext::Term& D = k < H.na ? C.a[k] : C.b[k - H.na];
-            if (T.col != MS_EXT_NONE && (T.col < 0 || (unsigned)T.col >= nbase)) return fail(MS_ERR_INVALID, "%s: column %u: term column %d out of range (%u)", me, e, T.col, nbase);
-            if (T.chal != MS_EXT_NONE && (T.chal < 0 || (unsigned)T.chal >= nchallenges)) return fail(MS_ERR_INVALID, "%s: column %u: term challenge %d out of range (%u)", me, e, T.chal, nchallenges);
-            if (T.sign != 1 && T.sign != -1) return fail(MS_ERR_INVALID, "%s: column %u: a term's sign is +1 or -1, not %d", me, e, T.sign);
-            D.col = T.col != MS_EXT_NONE ? (const uint64_t*)d_base[T.col] : nullptr;
-            if (n) { long long m = (long long)T.off % (long long)n; if (m < 0) m += (long long)n; D.off = (uint64_t)m; }
-            D.chal = T.chal; D.sign = T.sign;
-            if (D.col) term_bytes += 8.0 * n * VB;
-        }
+        for (unsigned k = 0; k < H.na + H.nb; k++, at++)
+            MSCHK(msextargs::resolve_term(R, e, ht[at], nchallenges, n, VB, k < H.na ? &C.a[k] : &C.b[k - H.na], &term_bytes));
     }
     if (n == 0 || next == 0) return MS_OK;
     const size_t nblocks = (n + msext::ROWS - 1) / msext::ROWS;
     if (nblocks > 0x7FFFFFFFull) return fail(MS_ERR_UNSUPPORTED, "%s: column too long", me);
-    const size_t out_bytes = n * VE * 8;
-    for (unsigned e = 0; e < next; e++) {
-        for (unsigned c = 0; c < nbase; c++)
-            if (ranges_overlap(d_out[e], out_bytes, d_base[c], n * VB * 8)) return fail(MS_ERR_INVALID, "%s: output column %u and base column %u overlap", me, e, c);
-        for (unsigned f = 0; f < e; f++)
-            if (ranges_overlap(d_out[e], out_bytes, d_out[f], out_bytes)) return fail(MS_ERR_INVALID, "%s: output columns %u and %u overlap", me, f, e);
-        if (ranges_overlap(d_out[e], out_bytes, d_challenges, (size_t)nchallenges * VE * 8)) return fail(MS_ERR_INVALID, "%s: output column %u and d_challenges overlap", me, e);
-    }
+    MSCHK(msextargs::output_overlaps(R, n, VB, VE, d_challenges, nchallenges, d_out, next));
     MSCHK(canon_cols(ctx, me, "d_base", base_field, n, d_base, nbase));
     MSCHK(canon_col(ctx, me, "d_challenges", ext_field, nchallenges, d_challenges));
     std::lock_guard<std::mutex> lk(ctx->mu);

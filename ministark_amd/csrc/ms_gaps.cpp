@@ -7,22 +7,9 @@
 static_assert(msgap::MAXGROUP == (int)MS_GAP_MAX_GROUP && msgap::MAXCOLS == (int)MS_GAP_MAX_COLUMNS, "gap_kernels.h and the header disagree");
 static_assert(msgap::COPY == (int)MS_GAP_COPY && msgap::ZERO == (int)MS_GAP_ZERO && msgap::COUNTER == (int)MS_GAP_COUNTER && msgap::FLAG == (int)MS_GAP_FLAG,
               "gap_kernels.h and the header disagree on the column kinds");
-static_assert(msgap::MASK_ALWAYS == (int)MS_EXT_ALWAYS && msgap::MASK_IF_NONZERO == (int)MS_EXT_IF_NONZERO && msgap::MASK_IF_ZERO == (int)MS_EXT_IF_ZERO,
-              "gap_kernels.h and the extension header disagree");
 static_assert(sizeof(msgap::Report) == sizeof(ms_gap_report) && sizeof(ms_gap_report) == 64 && sizeof(ms_gap_spec) == 32 && sizeof(ms_gap_column) == 8, "record layouts");
 static_assert(offsetof(msgap::Report, first_unordered) == offsetof(ms_gap_report, first_unordered) && offsetof(ms_gap_report, first_unordered) == 40, "record layouts");
 static_assert(sizeof(msgap::FillParams) <= 4096, "the fill's arguments travel by value");
-
-static int gap_checked(ms_ctx* ctx, const char* me, int field, size_t n_src, const void* const* d_base, const std::vector<unsigned>& used) {
-    std::vector<const void*> tab;
-    for (unsigned c : used) tab.push_back(d_base[c]);
-    ms_canon_report r;
-    MSCHK(ms_check_canonical(ctx, field, n_src, tab.data(), (unsigned)tab.size(), &r));
-    if (r.count)
-        return fail(MS_ERR_INVALID, "%s: d_base holds an element that is not canonical (>= p): column %u, row %llu; nothing was enqueued (checked mode)",
-                    me, used[r.first_col], (unsigned long long)r.first_row);
-    return MS_OK;
-}
 
 extern "C" int ms_gap_plan(ms_ctx* ctx, int field, size_t n_src, const void* const* d_base, unsigned nbase, const void* h_spec, const void* d_perm,
                            size_t n, void* d_start, void* d_report) {
@@ -31,42 +18,28 @@ extern "C" int ms_gap_plan(ms_ctx* ctx, int field, size_t n_src, const void* con
     unsigned V = 0;
     MSCHK(field_words(field, &V));
     if (V == 3) return fail(MS_ERR_UNSUPPORTED, "%s: the columns are those of a base trace, over Fp or Fp252, not Fq3", me);
-    for (unsigned c = 0; c < nbase; c++) if (!d_base[c]) return fail(MS_ERR_INVALID, "%s: null base column %u", me, c);
+    BaseColumns R(me, d_base, nbase);                                 // R.used: the base columns the spec names
+    MSCHK(R.null_check());
     const ms_gap_spec& H = *(const ms_gap_spec*)h_spec;
     if (H.ngroup < 0 || H.ngroup > (int)MS_GAP_MAX_GROUP) return fail(MS_ERR_INVALID, "%s: a group has 0 .. %d columns, not %d", me, MS_GAP_MAX_GROUP, H.ngroup);
     msgap::PlanParams P;
     memset(&P, 0, sizeof P);
-    std::vector<unsigned> used;                                       // the base columns the spec names
-    auto name = [&](int c) { if (std::find(used.begin(), used.end(), (unsigned)c) == used.end()) used.push_back((unsigned)c); };
-    for (int g = 0; g < H.ngroup; g++) {
-        if (H.group[g] < 0 || (unsigned)H.group[g] >= nbase) return fail(MS_ERR_INVALID, "%s: group column %d out of range (%u)", me, H.group[g], nbase);
-        P.group[g] = (const uint64_t*)d_base[H.group[g]];
-        name(H.group[g]);
-    }
-    if (H.counter >= 0) {
-        if ((unsigned)H.counter >= nbase) return fail(MS_ERR_INVALID, "%s: counter column %d out of range (%u)", me, H.counter, nbase);
-        P.counter = (const uint64_t*)d_base[H.counter];
-        name(H.counter);
-    }
-    if (H.mask < MS_EXT_ALWAYS || H.mask > MS_EXT_IF_ZERO) return fail(MS_ERR_INVALID, "%s: unknown mask kind %d", me, H.mask);
-    if (H.mask != MS_EXT_ALWAYS) {
-        if (H.mask_col < 0 || (unsigned)H.mask_col >= nbase) return fail(MS_ERR_INVALID, "%s: mask column %d out of range (%u)", me, H.mask_col, nbase);
-        P.mask = (const uint64_t*)d_base[H.mask_col];
-        name(H.mask_col);
-    }
+    for (int g = 0; g < H.ngroup; g++) MSCHK(R.col(H.group[g], "group ", &P.group[g]));
+    if (H.counter >= 0) MSCHK(R.col(H.counter, "counter ", &P.counter));
+    MSCHK(R.mask(H.mask, H.mask_col, "", &P.mask));
     P.mask_kind = H.mask;
     P.ngroup = P.counter ? (uint32_t)H.ngroup : 0u;                   // without a counter no gap is computed: the groups are not read
     if (n > ((size_t)1 << 30)) return fail(MS_ERR_UNSUPPORTED, "%s: %zu positions (at most 2^30)", me, n);
     if (n_src > ((size_t)1 << 32)) return fail(MS_ERR_UNSUPPORTED, "%s: %zu source rows (at most 2^32: an index is 32 bits)", me, n_src);
     const size_t col_bytes = n_src * V * 8, perm_bytes = n * 4, start_bytes = (n + 1) * 8;
-    for (unsigned c : used) {
+    for (unsigned c : R.used) {
         if (ranges_overlap(d_start, start_bytes, d_base[c], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_start and base column %u, which the spec names, overlap", me, c);
         if (ranges_overlap(d_report, sizeof(ms_gap_report), d_base[c], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_report and base column %u overlap", me, c);
     }
     if (d_perm && ranges_overlap(d_start, start_bytes, d_perm, perm_bytes)) return fail(MS_ERR_INVALID, "%s: d_start and d_perm overlap", me);
     if (d_perm && ranges_overlap(d_report, sizeof(ms_gap_report), d_perm, perm_bytes)) return fail(MS_ERR_INVALID, "%s: d_report and d_perm overlap", me);
     if (ranges_overlap(d_start, start_bytes, d_report, sizeof(ms_gap_report))) return fail(MS_ERR_INVALID, "%s: d_start and d_report overlap", me);
-    if (ctx->checked && n && n_src) MSCHK(gap_checked(ctx, me, field, n_src, d_base, used));
+    if (n) MSCHK(canon_named(ctx, me, field, n_src, d_base, R.used));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     { ProfScope ps(ctx, "gap_clear", (double)sizeof(ms_gap_report));
@@ -103,27 +76,27 @@ extern "C" int ms_gap_fill(ms_ctx* ctx, int field, size_t n_src, const void* con
     MSCHK(field_words(field, &V));
     if (V == 3) return fail(MS_ERR_UNSUPPORTED, "%s: the columns are those of a base trace, over Fp or Fp252, not Fq3", me);
     if (ncols == 0 || ncols > (unsigned)MS_GAP_MAX_COLUMNS) return fail(MS_ERR_INVALID, "%s: 1 .. %d columns, not %u", me, MS_GAP_MAX_COLUMNS, ncols);
-    for (unsigned c = 0; c < nbase; c++) if (!d_base[c]) return fail(MS_ERR_INVALID, "%s: null base column %u", me, c);
+    BaseColumns R(me, d_base, nbase);                                 // R.used: the base columns a record names
+    MSCHK(R.null_check());
     const ms_gap_column* H = (const ms_gap_column*)h_columns;
     msgap::FillParams P;
     memset(&P, 0, sizeof P);
-    std::vector<unsigned> used;                                       // the base columns a record names
     for (unsigned c = 0; c < ncols; c++) {
         if (!d_dst[c]) return fail(MS_ERR_INVALID, "%s: null destination %u", me, c);
         if (H[c].kind < MS_GAP_COPY || H[c].kind > MS_GAP_FLAG) return fail(MS_ERR_INVALID, "%s: column %u: unknown kind %d", me, c, H[c].kind);
         P.kind[c] = (uint8_t)H[c].kind;
         P.dst[c] = (uint64_t*)d_dst[c];
         if (H[c].kind == MS_GAP_FLAG) continue;
-        if (H[c].src < 0 || (unsigned)H[c].src >= nbase) return fail(MS_ERR_INVALID, "%s: column %u: source column %d out of range (%u)", me, c, H[c].src, nbase);
-        P.src[c] = (const uint64_t*)d_base[H[c].src];
-        if (std::find(used.begin(), used.end(), (unsigned)H[c].src) == used.end()) used.push_back((unsigned)H[c].src);
+        char what[32];
+        snprintf(what, sizeof what, "column %u: source ", c);
+        MSCHK(R.col(H[c].src, what, &P.src[c]));
     }
     if (n > ((size_t)1 << 30)) return fail(MS_ERR_UNSUPPORTED, "%s: %zu positions (at most 2^30)", me, n);
     if (n_out > ((size_t)1 << 30)) return fail(MS_ERR_UNSUPPORTED, "%s: %zu output rows (at most 2^30)", me, n_out);
     if (n_src > ((size_t)1 << 32)) return fail(MS_ERR_UNSUPPORTED, "%s: %zu source rows (at most 2^32: an index is 32 bits)", me, n_src);
     const size_t col_bytes = n_src * V * 8, dst_bytes = n_out * V * 8, perm_bytes = n * 4, start_bytes = (n + 1) * 8;
     for (unsigned c = 0; c < ncols; c++) {                            // lanes read any row of any source while others store
-        for (unsigned s : used)
+        for (unsigned s : R.used)
             if (ranges_overlap(d_dst[c], dst_bytes, d_base[s], col_bytes)) return fail(MS_ERR_INVALID, "%s: destination %u and base column %u overlap", me, c, s);
         if (d_perm && ranges_overlap(d_dst[c], dst_bytes, d_perm, perm_bytes)) return fail(MS_ERR_INVALID, "%s: destination %u and d_perm overlap", me, c);
         if (ranges_overlap(d_dst[c], dst_bytes, d_start, start_bytes)) return fail(MS_ERR_INVALID, "%s: destination %u and d_start overlap", me, c);
@@ -131,7 +104,7 @@ extern "C" int ms_gap_fill(ms_ctx* ctx, int field, size_t n_src, const void* con
             if (ranges_overlap(d_dst[c], dst_bytes, d_dst[s], dst_bytes)) return fail(MS_ERR_INVALID, "%s: destinations %u and %u overlap", me, s, c);
     }
     if (n_out == 0) return MS_OK;
-    if (ctx->checked && n && n_src && !used.empty()) MSCHK(gap_checked(ctx, me, field, n_src, d_base, used));
+    if (n) MSCHK(canon_named(ctx, me, field, n_src, d_base, R.used));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     using namespace msgap;

@@ -1,5 +1,7 @@
-// Internal declarations shared by the translation units of libministark_hip.so (ms_core / ms_ntt / ms_hash / ms_stage /
-// ms_eval / ms_deep / ms_comm / ms_coin / ms_rpo_coin .cpp): the context, the plan object, error plumbing, pooled scratch.  Not part of the C ABI.
+// Internal declarations shared by the translation units of libministark_hip.so (ms_core / ms_ntt / ms_stage / ms_hash / ms_eval / ms_deep /
+// ms_comm / ms_validate / ms_blake2s / ms_canon / ms_coin / ms_keccak / ms_ext / ms_logup / ms_rpo_coin / ms_lookup / ms_sort / ms_gaps .cpp,
+// the SOURCES of build.py): the context, the plan object, error plumbing, pooled scratch, the checked mode's scans and the base-column
+// arguments of the trace-table entry points.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -200,6 +202,22 @@ int canon_program(ms_ctx* ctx, const char* entry, bool is252, const uint32_t* h_
                   unsigned log_n, const void* h_domain_offset, const void* d_x_lde, const void* const* d_base_cols, unsigned nbase,
                   const void* const* d_ext_cols, unsigned next, const void* const* d_periodic, const unsigned* periodic_len, unsigned nperiodic);
 static inline int field_of_words(unsigned V) { return V == 1 ? MS_GOLDILOCKS_FP : V == 3 ? MS_GOLDILOCKS_FQ3 : MS_STARK252_FP; }
+// d_base[c] for c in `used` alone (what a call NAMES; the rest of d_base may hold anything); the refusal reports the caller's own column index
+int canon_named(ms_ctx* ctx, const char* entry, int field, size_t n, const void* const* d_base, const std::vector<unsigned>& used);
+
+// ms_core.cpp: the base-column table (d_base, nbase) of a trace-table entry point (ms_ext / ms_logup / ms_lookup / ms_sort / ms_gaps .cpp):
+// resolves the column indices of the caller's records to addresses, refuses the ones out of range, and keeps the list of the columns
+// named, in the order first named -- what the overlap checks and canon_named go through.  `what` / `who` open the refusal after
+// "<entry>: " and end in a space or in ": " ("key ", "lookup set 1: ", "column 3: term ").
+struct BaseColumns {
+    const char* me; const void* const* d_base; unsigned nbase;
+    std::vector<unsigned> used;
+    BaseColumns(const char* entry, const void* const* base, unsigned n) : me(entry), d_base(base), nbase(n) {}
+    int null_check() const;                                                     // "null base column %u"
+    int col(int index, const char* what, const uint64_t** ptr);                // "<what>column %d out of range (%u)"
+    // the mask words of a record: *ptr is null for MS_EXT_ALWAYS, whose mask_col is not looked at
+    int mask(int kind, int mask_col, const char* who, const uint64_t** ptr);   // "<who>unknown mask kind %d", "<who>mask column %d out of range (%u)"
+};
 
 // ms_ntt.cpp
 int ctx_plan(ms_ctx* ctx, unsigned V, unsigned log_n, bool inverse, uint64_t h, ms_ntt_plan** out);     // the context's cached plan

@@ -4,8 +4,6 @@
 #include "lookup_kernels.h"
 
 static_assert(mslk::MAXW == (int)MS_LOOKUP_MAX_WIDTH && mslk::MAXSETS == (int)MS_LOOKUP_MAX_SETS, "lookup_kernels.h and the header disagree");
-static_assert(mslk::MASK_ALWAYS == (int)MS_EXT_ALWAYS && mslk::MASK_IF_NONZERO == (int)MS_EXT_IF_NONZERO && mslk::MASK_IF_ZERO == (int)MS_EXT_IF_ZERO,
-              "lookup_kernels.h and the extension header disagree");
 static_assert(sizeof(mslk::Report) == sizeof(ms_lookup_report) && sizeof(ms_lookup_report) == 32 && sizeof(ms_lookup_tuple) == 32, "record layouts");
 
 template <int V, class F>
@@ -36,33 +34,23 @@ extern "C" int ms_lookup_multiplicities(ms_ctx* ctx, int field, size_t n, const 
     if (V == 3) return fail(MS_ERR_UNSUPPORTED, "%s: tuples are rows of a base trace, over Fp or Fp252, not Fq3", me);
     if (width == 0 || width > (unsigned)MS_LOOKUP_MAX_WIDTH) return fail(MS_ERR_INVALID, "%s: a tuple has 1 .. %d components, not %u", me, MS_LOOKUP_MAX_WIDTH, width);
     if (nsets > (unsigned)MS_LOOKUP_MAX_SETS) return fail(MS_ERR_UNSUPPORTED, "%s: %u lookup sets in one call (at most %d)", me, nsets, MS_LOOKUP_MAX_SETS);
-    for (unsigned c = 0; c < nbase; c++) if (!d_base[c]) return fail(MS_ERR_INVALID, "%s: null base column %u", me, c);
+    BaseColumns R(me, d_base, nbase);                                 // R.used: the base columns a tuple or a mask names
+    MSCHK(R.null_check());
     mslk::Params P;
     memset(&P, 0, sizeof P);
-    std::vector<unsigned> used;                                       // the base columns a tuple or a mask names
-    auto name = [&](int c) { if (std::find(used.begin(), used.end(), (unsigned)c) == used.end()) used.push_back((unsigned)c); };
     for (unsigned s = 0; s <= nsets; s++) {                           // the table, then the sets
         const ms_lookup_tuple& H = s ? ((const ms_lookup_tuple*)h_lookups)[s - 1] : *(const ms_lookup_tuple*)h_table;
         mslk::Tuple& T = s ? P.sets[s - 1] : P.table;
         char who[32];
-        if (s) snprintf(who, sizeof who, "lookup set %u", s - 1); else snprintf(who, sizeof who, "the table");
-        for (unsigned c = 0; c < width; c++) {
-            if (H.cols[c] < 0 || (unsigned)H.cols[c] >= nbase) return fail(MS_ERR_INVALID, "%s: %s: column %d out of range (%u)", me, who, H.cols[c], nbase);
-            T.cols[c] = (const uint64_t*)d_base[H.cols[c]];
-            name(H.cols[c]);
-        }
-        if (H.mask < MS_EXT_ALWAYS || H.mask > MS_EXT_IF_ZERO) return fail(MS_ERR_INVALID, "%s: %s: unknown mask kind %d", me, who, H.mask);
-        if (H.mask != MS_EXT_ALWAYS) {
-            if (H.mask_col < 0 || (unsigned)H.mask_col >= nbase) return fail(MS_ERR_INVALID, "%s: %s: mask column %d out of range (%u)", me, who, H.mask_col, nbase);
-            T.mask = (const uint64_t*)d_base[H.mask_col];
-            name(H.mask_col);
-        }
+        if (s) snprintf(who, sizeof who, "lookup set %u: ", s - 1); else snprintf(who, sizeof who, "the table: ");
+        for (unsigned c = 0; c < width; c++) MSCHK(R.col(H.cols[c], who, &T.cols[c]));
+        MSCHK(R.mask(H.mask, H.mask_col, who, &T.mask));
         T.mask_kind = H.mask;
     }
     if (n > ((size_t)1 << 30)) return fail(MS_ERR_UNSUPPORTED, "%s: %zu rows (at most 2^30: a slot is a 32-bit row index)", me, n);
     if ((unsigned long long)nsets * n >= (1ull << 32)) return fail(MS_ERR_UNSUPPORTED, "%s: %u sets of %zu rows (the counters are 32-bit: sets * rows < 2^32)", me, nsets, n);
     const size_t col_bytes = n * V * 8;
-    for (unsigned c : used) {
+    for (unsigned c : R.used) {
         if (ranges_overlap(d_m, col_bytes, d_base[c], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_m and base column %u, which a tuple or a mask names, overlap", me, c);
         if (ranges_overlap(d_report, sizeof(ms_lookup_report), d_base[c], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_report and base column %u overlap", me, c);
     }
@@ -73,15 +61,7 @@ extern "C" int ms_lookup_multiplicities(ms_ctx* ctx, int field, size_t n, const 
         HIPCHK(hipMemsetAsync(d_report, 0, sizeof(ms_lookup_report), ctx->stream));
         return MS_OK;
     }
-    if (ctx->checked) {                                               // only what the call reads: d_m may be a column of d_base, of any content
-        std::vector<const void*> tab;
-        for (unsigned c : used) tab.push_back(d_base[c]);
-        ms_canon_report r;
-        MSCHK(ms_check_canonical(ctx, field, n, tab.data(), (unsigned)tab.size(), &r));
-        if (r.count)
-            return fail(MS_ERR_INVALID, "%s: d_base holds an element that is not canonical (>= p): column %u, row %llu; nothing was enqueued (checked mode)",
-                        me, used[r.first_col], (unsigned long long)r.first_row);
-    }
+    MSCHK(canon_named(ctx, me, field, n, d_base, R.used));            // only what the call reads: d_m may be a column of d_base, of any content
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     LockedPoolGuard pooled(ctx);

@@ -5,8 +5,6 @@
 #include "sort_kernels.h"
 
 static_assert(mssort::MAXK == (int)MS_SORT_MAX_KEYS && mssort::MAXCOLS == (int)MS_PERMUTE_MAX_COLUMNS, "sort_kernels.h and the header disagree");
-static_assert(mssort::MASK_ALWAYS == (int)MS_EXT_ALWAYS && mssort::MASK_IF_NONZERO == (int)MS_EXT_IF_NONZERO && mssort::MASK_IF_ZERO == (int)MS_EXT_IF_ZERO,
-              "sort_kernels.h and the extension header disagree");
 static_assert(sizeof(mssort::Report) == sizeof(ms_sort_report) && sizeof(ms_sort_report) == 16 && sizeof(ms_sort_key) == 32, "record layouts");
 static_assert(sizeof(mssort::PermuteParams) <= 4096, "the gather's arguments travel by value");
 
@@ -58,27 +56,17 @@ extern "C" int ms_sort_rows(ms_ctx* ctx, int field, size_t n, const void* const*
     MSCHK(field_words(field, &V));
     if (V == 3) return fail(MS_ERR_UNSUPPORTED, "%s: keys are columns of a base trace, over Fp or Fp252, not Fq3", me);
     if (nkeys == 0 || nkeys > (unsigned)MS_SORT_MAX_KEYS) return fail(MS_ERR_INVALID, "%s: a key has 1 .. %d components, not %u", me, MS_SORT_MAX_KEYS, nkeys);
-    for (unsigned c = 0; c < nbase; c++) if (!d_base[c]) return fail(MS_ERR_INVALID, "%s: null base column %u", me, c);
+    BaseColumns R(me, d_base, nbase);                                 // R.used: the base columns the key or the mask names
+    MSCHK(R.null_check());
     const ms_sort_key& H = *(const ms_sort_key*)h_key;
     mssort::Params P;
     memset(&P, 0, sizeof P);
-    std::vector<unsigned> used;                                       // the base columns the key or the mask names
-    auto name = [&](int c) { if (std::find(used.begin(), used.end(), (unsigned)c) == used.end()) used.push_back((unsigned)c); };
-    for (unsigned k = 0; k < nkeys; k++) {
-        if (H.cols[k] < 0 || (unsigned)H.cols[k] >= nbase) return fail(MS_ERR_INVALID, "%s: key column %d out of range (%u)", me, H.cols[k], nbase);
-        P.cols[k] = (const uint64_t*)d_base[H.cols[k]];
-        name(H.cols[k]);
-    }
-    if (H.mask < MS_EXT_ALWAYS || H.mask > MS_EXT_IF_ZERO) return fail(MS_ERR_INVALID, "%s: unknown mask kind %d", me, H.mask);
-    if (H.mask != MS_EXT_ALWAYS) {
-        if (H.mask_col < 0 || (unsigned)H.mask_col >= nbase) return fail(MS_ERR_INVALID, "%s: mask column %d out of range (%u)", me, H.mask_col, nbase);
-        P.mask = (const uint64_t*)d_base[H.mask_col];
-        name(H.mask_col);
-    }
+    for (unsigned k = 0; k < nkeys; k++) MSCHK(R.col(H.cols[k], "key ", &P.cols[k]));
+    MSCHK(R.mask(H.mask, H.mask_col, "", &P.mask));
     P.mask_kind = H.mask;
     if (n > ((size_t)1 << 30)) return fail(MS_ERR_UNSUPPORTED, "%s: %zu rows (at most 2^30: an index is 32 bits)", me, n);
     const size_t col_bytes = n * V * 8, perm_bytes = n * 4;
-    for (unsigned c : used) {
+    for (unsigned c : R.used) {
         if (ranges_overlap(d_perm, perm_bytes, d_base[c], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_perm and base column %u, which the key or the mask names, overlap", me, c);
         if (ranges_overlap(d_report, sizeof(ms_sort_report), d_base[c], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_report and base column %u overlap", me, c);
     }
@@ -89,15 +77,7 @@ extern "C" int ms_sort_rows(ms_ctx* ctx, int field, size_t n, const void* const*
         HIPCHK(hipMemsetAsync(d_report, 0, sizeof(ms_sort_report), ctx->stream));
         return MS_OK;
     }
-    if (ctx->checked) {                                               // only what the call reads
-        std::vector<const void*> tab;
-        for (unsigned c : used) tab.push_back(d_base[c]);
-        ms_canon_report r;
-        MSCHK(ms_check_canonical(ctx, field, n, tab.data(), (unsigned)tab.size(), &r));
-        if (r.count)
-            return fail(MS_ERR_INVALID, "%s: d_base holds an element that is not canonical (>= p): column %u, row %llu; nothing was enqueued (checked mode)",
-                        me, used[r.first_col], (unsigned long long)r.first_row);
-    }
+    MSCHK(canon_named(ctx, me, field, n, d_base, R.used));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     LockedPoolGuard pooled(ctx);

@@ -29,26 +29,20 @@
 //                  pass moves, when the flag pass ran
 //   permute_columns  dst[c][i] = src[c][index[i]], zero for index[i] >= n_src
 #pragma once
-#include "stage_kernels.h"
+#include "table_common.h"
 
 namespace mssort {
 
 static constexpr int NT = 256, MAXK = 4, ITEMS = 8, TILE = NT * ITEMS, WAVES = NT / 64, WAVE_ROWS = 64 * ITEMS, SCAN_ROUND = NT;
 static constexpr int MAXWORDS = MAXK * 4, MAXPOS = MAXWORDS * 8, PREPARE_MAX_GRID = 1024, MAXCOLS = 128;
 static constexpr uint32_t FLAG_POS = 0xFFFFFFFFu;
-static constexpr int MASK_ALWAYS = 0, MASK_IF_NONZERO = 1, MASK_IF_ZERO = 2;
-
-#ifdef MS_EMU
-static inline void add(uint32_t* p, uint32_t v) { *p += v; }
-static inline void add(uint64_t* p, uint64_t v) { *p += v; }
-static inline void aor(uint64_t* p, uint64_t v) { *p |= v; }
-static inline void aand(uint64_t* p, uint64_t v) { *p &= v; }
-#else
-static __device__ __forceinline__ void add(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
-static __device__ __forceinline__ void add(uint64_t* p, uint64_t v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
-static __device__ __forceinline__ void aor(uint64_t* p, uint64_t v) { atomicOr((unsigned long long*)p, (unsigned long long)v); }
-static __device__ __forceinline__ void aand(uint64_t* p, uint64_t v) { atomicAnd((unsigned long long*)p, (unsigned long long)v); }
-#endif
+using mstab::MASK_ALWAYS;
+using mstab::mask_holds;
+using mstab::Canon;
+using mstab::add;
+using mstab::aor;
+using mstab::aand;
+using mstab::block_exclusive;
 
 struct Report { uint64_t active, varying_bytes; };
 struct Table {
@@ -73,24 +67,6 @@ struct Params {
 };
 
 template <int V>
-__device__ __forceinline__ bool active(const Params& P, size_t i) {
-    if (P.mask_kind == MASK_ALWAYS) return true;
-    uint64_t any = 0;
-    #pragma unroll
-    for (int l = 0; l < V; l++) any |= P.mask[i * V + l];
-    return (any == 0) == (P.mask_kind == MASK_IF_ZERO);
-}
-
-template <int V> struct Canon;
-template <> struct Canon<1> { static __device__ __forceinline__ void words(const uint64_t* col, size_t i, uint64_t* w) { w[0] = gl::from_mont(col[i]); } };
-template <> struct Canon<4> {
-    static __device__ __forceinline__ void words(const uint64_t* col, size_t i, uint64_t* w) {
-        const f252::E c = f252::from_mont(msstage::Fp252T::load(col, i));
-        w[0] = c.l[0]; w[1] = c.l[1]; w[2] = c.l[2]; w[3] = c.l[3];
-    }
-};
-
-template <int V>
 __global__ void __launch_bounds__(NT) sort_prepare(Params P) {
     __shared__ uint64_t s_or[MAXWORDS], s_and[MAXWORDS];
     __shared__ uint32_t s_active;
@@ -103,7 +79,7 @@ __global__ void __launch_bounds__(NT) sort_prepare(Params P) {
     __syncthreads();
     const size_t n = P.n;
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
-        const bool act = active<V>(P, i);
+        const bool act = mask_holds<V>(P.mask, P.mask_kind, i);
         if (P.flag) P.flag[i] = act ? 0 : 1;
         P.perm[0][i] = (uint32_t)i;
         nact += act;
@@ -223,38 +199,13 @@ __global__ void __launch_bounds__(NT) pass_hist(Params P, uint32_t pos) {
     P.hist[(size_t)threadIdx.x * P.ntiles + blockIdx.x] = s_hist[threadIdx.x];
 }
 
-// exclusive prefix over the blockDim.x values v of a workgroup (one per thread; 64, 128 or 256 of them), through LDS; every thread calls it
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* s_a, uint32_t* s_b, uint32_t* sum) {
-    uint32_t *in = s_a, *out = s_b;
-    in[threadIdx.x] = v;
-    __syncthreads();
-    for (unsigned d = 1; d < blockDim.x; d <<= 1) {
-        out[threadIdx.x] = in[threadIdx.x] + (threadIdx.x >= d ? in[threadIdx.x - d] : 0u);
-        __syncthreads();
-        uint32_t* t = in; in = out; out = t;
-    }
-    const uint32_t incl = in[threadIdx.x];
-    *sum = in[blockDim.x - 1];
-    __syncthreads();                                                           // the buffers are free again after this
-    return incl - v;
-}
-
 // grid: 256 workgroups, one per digit, of scan_threads(ntiles) threads: a round takes as many tiles
 __host__ __device__ inline unsigned scan_threads(uint32_t ntiles) { return ntiles <= 64 ? 64u : ntiles <= 128 ? 128u : (unsigned)SCAN_ROUND; }
 __global__ void __launch_bounds__(NT) pass_scan(Params P, uint32_t pos) {
     const Pass ps = pass_of(P, pos);
     if (ps.skip) return;
     __shared__ uint32_t s_a[NT], s_b[NT];
-    uint32_t* h = P.hist + (size_t)blockIdx.x * P.ntiles;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < P.ntiles; base += blockDim.x) {
-        const uint32_t t = base + threadIdx.x;
-        const uint32_t v = t < P.ntiles ? h[t] : 0u;
-        uint32_t sum;
-        const uint32_t ex = block_exclusive(v, s_a, s_b, &sum);
-        if (t < P.ntiles) h[t] = carry + ex;
-        carry += sum;
-    }
+    const uint32_t carry = mstab::prefix_in_rounds(P.hist + (size_t)blockIdx.x * P.ntiles, P.ntiles, blockDim.x, s_a, s_b);
     if (threadIdx.x == 0) P.total[blockIdx.x] = carry;
 }
 
@@ -268,7 +219,7 @@ __global__ void __launch_bounds__(NT) pass_scatter(Params P, uint32_t pos) {
     #pragma unroll
     for (int w = 0; w < WAVES; w++) s_cnt[w][threadIdx.x] = 0;
     uint32_t sum;
-    const uint32_t first = block_exclusive(P.total[threadIdx.x], s_a, s_b, &sum)                  // the barriers in it publish the zeros too
+    const uint32_t first = block_exclusive(P.total[threadIdx.x], blockDim.x, s_a, s_b, &sum)                  // the barriers in it publish the zeros too
                            + P.hist[(size_t)threadIdx.x * P.ntiles + blockIdx.x];
     uint32_t dig[ITEMS], rank[ITEMS];
     #pragma unroll

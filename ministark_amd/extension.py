@@ -41,6 +41,15 @@ LOOKUP_MAX_WIDTH, LOOKUP_MAX_SETS = 4, 8
 SORT_MAX_KEYS, PERMUTE_MAX_COLUMNS = 4, 128
 
 
+def _mask_words(who, mask):
+    """mask=None | ("nonzero", m) | ("zero", m) of class `who` -> (kind, column): the mask and mask_col words of its record"""
+    if mask is None:
+        return (0, 0)
+    if len(mask) != 2 or mask[0] not in _MASK:
+        raise ValueError(f"{who}: mask is None, ('nonzero', m) or ('zero', m), not {mask!r}")
+    return (_MASK[mask[0]], int(mask[1]))
+
+
 class ExtColumn:
     """One extension column.  init: 0, 1, or ("challenge", k);  a_terms / b_terms: lists of terms (an empty A is 1, an empty B is 0);
     mask: None (every row is active), ("nonzero", m) or ("zero", m): active where base column m is != 0 / == 0 (the processor and memory
@@ -61,13 +70,7 @@ class ExtColumn:
             init = (_INIT[self.init], 0)
         else:
             raise ValueError(f"{who}: init is 0, 1 or ('challenge', k), not {self.init!r}")
-        if self.mask is None:
-            mask = (0, 0)
-        else:
-            kind, m = self.mask
-            if kind not in _MASK:
-                raise ValueError(f"{who}: mask is None, ('nonzero', m) or ('zero', m), not {self.mask!r}")
-            mask = (_MASK[kind], int(m))
+        mask = _mask_words(who, self.mask)
         return [init[0], init[1], mask[0], mask[1], int(self.inclusive)]
 
     def _record(self):
@@ -172,12 +175,11 @@ class LookupTuple:
         self.cols, self.mask = [int(c) for c in cols], mask
         if not 1 <= len(self.cols) <= LOOKUP_MAX_WIDTH:
             raise ValueError(f"LookupTuple: a tuple has 1 .. {LOOKUP_MAX_WIDTH} columns, not {len(self.cols)}")
-        if mask is not None and (len(mask) != 2 or mask[0] not in _MASK):
-            raise ValueError(f"LookupTuple: mask is None, ('nonzero', m) or ('zero', m), not {mask!r}")
+        _mask_words("LookupTuple", mask)
 
     def _record(self):
         """the eight 32-bit words of ms_lookup_tuple: cols[4], mask, mask_col, pad0, pad1"""
-        mask = (0, 0) if self.mask is None else (_MASK[self.mask[0]], int(self.mask[1]))
+        mask = _mask_words("LookupTuple", self.mask)
         return self.cols + [0] * (LOOKUP_MAX_WIDTH - len(self.cols)) + [mask[0], mask[1], 0, 0]
 
 
@@ -272,12 +274,11 @@ class SortKey:
         self.cols, self.mask = [int(c) for c in cols], mask
         if not 1 <= len(self.cols) <= SORT_MAX_KEYS:
             raise ValueError(f"SortKey: a key has 1 .. {SORT_MAX_KEYS} columns, not {len(self.cols)}")
-        if mask is not None and (len(mask) != 2 or mask[0] not in _MASK):
-            raise ValueError(f"SortKey: mask is None, ('nonzero', m) or ('zero', m), not {mask!r}")
+        _mask_words("SortKey", mask)
 
     def _record(self):
         """the eight 32-bit words of ms_sort_key: cols[4], mask, mask_col, pad0, pad1"""
-        mask = (0, 0) if self.mask is None else (_MASK[self.mask[0]], int(self.mask[1]))
+        mask = _mask_words("SortKey", self.mask)
         return self.cols + [0] * (SORT_MAX_KEYS - len(self.cols)) + [mask[0], mask[1], 0, 0]
 
 
@@ -389,12 +390,11 @@ class GapSpec:
             raise ValueError(f"GapSpec: a group has 0 .. {GAP_MAX_GROUP} columns, not {len(self.group)}")
         if self.counter is not None and self.counter < 0:
             raise ValueError(f"GapSpec: counter is a column index or None, not {counter!r}")
-        if mask is not None and (len(mask) != 2 or mask[0] not in _MASK):
-            raise ValueError(f"GapSpec: mask is None, ('nonzero', m) or ('zero', m), not {mask!r}")
+        _mask_words("GapSpec", mask)
 
     def _record(self):
         """the eight 32-bit words of ms_gap_spec: group[3], ngroup, counter, mask, mask_col, pad0"""
-        mask = (0, 0) if self.mask is None else (_MASK[self.mask[0]], int(self.mask[1]))
+        mask = _mask_words("GapSpec", self.mask)
         return self.group + [0] * (GAP_MAX_GROUP - len(self.group)) + [len(self.group), NONE if self.counter is None else self.counter, mask[0], mask[1], 0]
 
 

@@ -97,14 +97,18 @@ def test_the_kernel_constants_are_the_headers_and_the_tests():
     assert "sizeof(ms_gap_report) == 64 && sizeof(ms_gap_spec) == 32 && sizeof(ms_gap_column) == 8" in host
     build = __import__("ministark_amd.build", fromlist=["SOURCES"])
     assert "ms_gaps.cpp" in build.SOURCES and HEADER in build._deps()
-    # the wrappers the simulator needs are plain read-modify-write there and the HIP atomics in the product
-    emu, hip = kernels[kernels.index("#ifdef MS_EMU"):kernels.index("#else")], kernels[kernels.index("#else"):kernels.index("#endif")]
+    # the wrappers the simulator needs are plain read-modify-write there and the HIP atomics in the product: the one set of table_common.h
+    common = open(os.path.join(csrc, "table_common.h")).read()
+    emu, hip = common[common.index("#ifdef MS_EMU"):common.index("#else")], common[common.index("#else"):common.index("#endif")]
     for fn in ("add", "amax", "amin"):
-        assert re.search(r"\b%s\(" % fn, emu) and re.search(r"\b%s\(" % fn, hip), fn
+        assert re.search(r"\b%s\(" % fn, emu) and re.search(r"\b%s\(" % fn, hip) and "using mstab::%s;" % fn in kernels, fn
     assert "atomic" not in emu and all(a in hip for a in ("atomicAdd", "atomicMax", "atomicMin"))
-    # no position comes from an atomic: the kernels that write start[] past the counts and the fill name none
-    rest = kernels[kernels.index("__device__ __forceinline__ uint64_t block_exclusive64"):]
-    assert "add(&" not in rest and "amax(" not in rest and "amin(" not in rest and "atomic" not in rest
+    # no position comes from an atomic: the kernels that write start[] past the counts and the fill name none, nor do the prefixes they call
+    rest = kernels[kernels.index("__global__ void __launch_bounds__(NT) gap_scan"):]
+    prefixes = common[common.index("__device__ __forceinline__ T block_exclusive"):]
+    for text in (rest, prefixes):
+        assert "add(&" not in text and "amax(" not in text and "amin(" not in text and "atomic" not in text
+    assert "block_exclusive(" in rest and "prefix_in_rounds(" in rest and "T prefix_in_rounds(" in prefixes
 
 
 def test_sys_gaps_rs_matches_the_header_and_the_generator():

@@ -84,10 +84,11 @@ def test_the_kernel_constants_are_the_headers():
     assert "static_assert(mslk::MAXW == (int)MS_LOOKUP_MAX_WIDTH && mslk::MAXSETS == (int)MS_LOOKUP_MAX_SETS" in host
     build = __import__("ministark_amd.build", fromlist=["SOURCES"])
     assert "ms_lookup.cpp" in build.SOURCES and HEADER in build._deps()
-    # the wrappers the simulator needs are plain read-modify-write there and the HIP atomics in the product
-    emu, hip = kernels[kernels.index("#ifdef MS_EMU"):kernels.index("#else")], kernels[kernels.index("#else"):kernels.index("#endif")]
+    # the wrappers the simulator needs are plain read-modify-write there and the HIP atomics in the product: the one set of table_common.h
+    common = open(os.path.join(csrc, "table_common.h")).read()
+    emu, hip = common[common.index("#ifdef MS_EMU"):common.index("#else")], common[common.index("#else"):common.index("#endif")]
     for fn in ("cas", "amin", "add", "peek"):
-        assert re.search(r"\b%s\(" % fn, emu) and re.search(r"\b%s\(" % fn, hip), fn
+        assert re.search(r"\b%s\(" % fn, emu) and re.search(r"\b%s\(" % fn, hip) and "using mstab::%s;" % fn in kernels, fn
     assert "atomic" not in emu and all(a in hip for a in ("atomicCAS", "atomicMin", "atomicAdd"))
 
 

@@ -92,10 +92,11 @@ def test_the_kernel_constants_are_the_headers_and_the_tests():
     assert "sizeof(ms_sort_report) == 16 && sizeof(ms_sort_key) == 32" in host
     build = __import__("ministark_amd.build", fromlist=["SOURCES"])
     assert "ms_sort.cpp" in build.SOURCES and HEADER in build._deps()
-    # the wrappers the simulator needs are plain read-modify-write there and the HIP atomics in the product
-    emu, hip = kernels[kernels.index("#ifdef MS_EMU"):kernels.index("#else")], kernels[kernels.index("#else"):kernels.index("#endif")]
+    # the wrappers the simulator needs are plain read-modify-write there and the HIP atomics in the product: the one set of table_common.h
+    common = open(os.path.join(csrc, "table_common.h")).read()
+    emu, hip = common[common.index("#ifdef MS_EMU"):common.index("#else")], common[common.index("#else"):common.index("#endif")]
     for fn in ("add", "aor", "aand"):
-        assert re.search(r"\b%s\(" % fn, emu) and re.search(r"\b%s\(" % fn, hip), fn
+        assert re.search(r"\b%s\(" % fn, emu) and re.search(r"\b%s\(" % fn, hip) and "using mstab::%s;" % fn in kernels, fn
     assert "atomic" not in emu and all(a in hip for a in ("atomicAdd", "atomicOr", "atomicAnd"))
     # no rank comes from an atomic: the scatter kernel names none
     scatter = kernels[kernels.index("__global__ void __launch_bounds__(NT) pass_scatter"):kernels.index("__global__ void __launch_bounds__(NT) sort_finish")]
