@@ -11,5 +11,6 @@ from .api import (GOLDILOCKS_FP, GOLDILOCKS_FQ3, STARK252_FP, GL_GENERATOR, GL_P
                   scan_affine, running_product, Queries)
 from .extension import (ExtColumn, LogUpColumn, LookupMissing, LookupReport, LookupTuple, build_extension_columns, build_logup_columns,  # noqa: F401
                         lookup_multiplicities, DeviceIndex, SortKey, SortReport, permute_columns, sort_rows,
-                        GapError, GapPlan, GapReport, GapSpec, gap_fill, gap_plan)
+                        GapError, GapPlan, GapReport, GapSpec, gap_fill, gap_plan,
+                        JoinReport, fetch_columns, join_rows)
 from .debug import ConstraintViolation, ValidationReport, compile_constraints, validate_constraints  # noqa: F401

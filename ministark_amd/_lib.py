@@ -64,6 +64,12 @@ class LookupTupleRecord(ctypes.Structure):
     _fields_ = [("cols", ctypes.c_int32 * 4), ("mask", ctypes.c_int32), ("mask_col", ctypes.c_int32), ("pad0", ctypes.c_int32), ("pad1", ctypes.c_int32)]
 
 
+class JoinReportRecord(ctypes.Structure):
+    """`ms_join_report` of include/ministark_hip_join.h: what ms_join_rows found."""
+    _fields_ = [("matched", ctypes.c_uint64), ("missing", ctypes.c_uint64), ("first_missing_row", ctypes.c_uint64), ("first_missing_set", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32), ("duplicate_table_rows", ctypes.c_uint64), ("table_active", ctypes.c_uint64)]
+
+
 class SortKeyRecord(ctypes.Structure):
     """`ms_sort_key` of include/ministark_hip_sort.h."""
     _fields_ = [("cols", ctypes.c_int32 * 4), ("mask", ctypes.c_int32), ("mask_col", ctypes.c_int32), ("pad0", ctypes.c_int32), ("pad1", ctypes.c_int32)]
@@ -232,9 +238,14 @@ class Lib:
             "ms_gap_plan": (i, [vp, i, sz, c_void_pp, u, vp, vp, sz, vp, vp]),
             "ms_gap_fill": (i, [vp, i, sz, c_void_pp, u, vp, sz, vp, vp, c_void_pp, u, sz]),
         }
+        # include/ministark_hip_join.h: rows joined against a table -- the matched row index, fetched by ms_permute_columns
+        join_sigs = {
+            "ms_join_rows": (i, [vp, i, sz, c_void_pp, u, vp, sz, c_void_pp, u, u, vp, u, c_void_pp, vp]),
+        }
         self.optional = {}
         for name, (res, args) in (list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items())
-                                  + list(logup_sigs.items()) + list(rpo_coin_sigs.items()) + list(lookup_sigs.items()) + list(sort_sigs.items()) + list(gap_sigs.items())):
+                                  + list(logup_sigs.items()) + list(rpo_coin_sigs.items()) + list(lookup_sigs.items()) + list(sort_sigs.items()) + list(gap_sigs.items())
+                                  + list(join_sigs.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -247,6 +258,7 @@ class Lib:
         self.lookup_sigs = lookup_sigs
         self.sort_sigs = sort_sigs
         self.gap_sigs = gap_sigs
+        self.join_sigs = join_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

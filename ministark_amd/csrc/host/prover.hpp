@@ -5,6 +5,7 @@
 //   ExtColumn / build_extension_columns   src/trace.rs build_extension_columns: every extension column in one call (ministark_hip_ext.h)
 //   LookupTuple / lookup_multiplicities   the m column of a LogUp lookup, counted on the device (ministark_hip_lookup.h)
 //   SortKey / sort_rows / permute_columns   the rows of a table in key order (examples/brainfuck/vm.rs sort_by_key), on the device (ministark_hip_sort.h)
+//   join_rows / fetch_columns         for every row, the table row that holds its key, and that row's other columns: instruction fetch, ROM reads (ministark_hip_join.h)
 //   GapSpec / gap_plan / gap_fill     derive_memory_rows and pad_*_rows (examples/brainfuck/vm.rs:282-380): select, fill clock gaps, pad, on the device (ministark_hip_gaps.h)
 //   Queries                           src/trace.rs:113-157
 //   grind_proof_of_work               src/random.rs:48-55
@@ -21,6 +22,7 @@
 #include "../../../include/ministark_hip_lookup.h"
 #include "../../../include/ministark_hip_sort.h"
 #include "../../../include/ministark_hip_gaps.h"
+#include "../../../include/ministark_hip_join.h"
 #include <cstring>
 #include <stdint.h>
 // host arithmetic of the 252-bit field (points and offsets of its composer): the library's own fp252.h, kept inside ms:: so that its
@@ -243,6 +245,62 @@ inline Matrix<F> permute_columns(const Matrix<F>& src, const RowOrder& order, si
     for (auto& c : out.columns) to.push_back(c.ptr());
     check(ms_permute_columns(pl.ctx(), F::id, src.num_rows(), in.data(), to.data(), (unsigned)in.size(), order.index.ptr(), n_out));
     return out;
+}
+
+// Rows joined against a table in one asynchronous call (ms_join_rows): match[s][i] = the smallest active row of `table` whose key
+// (`table_key`, indices into `table`) equals the key of row i of `base` under keys[s] (indices into `base`), or MS_JOIN_NONE for an inactive
+// row and for a key the table does not hold.  The two matrices may be the same one.  The matches are RowOrders: permute_columns reads them.
+struct JoinReport {
+    std::vector<RowOrder> matches;                               // one per key set; .report is not written (the join has one report: buf)
+    GpuVec<Fp> buf;                                              // the ms_join_report where the call wrote it
+    ms_join_report read() const { const std::vector<uint64_t> w = buf.to_host(); ms_join_report r; memcpy(&r, w.data(), sizeof r); return r; }   // a host wait
+};
+template <class B>
+inline JoinReport join_rows(const Matrix<B>& table, const LookupTuple& table_key, const Matrix<B>& base, const std::vector<LookupTuple>& keys) {
+    Planner& pl = base.planner();
+    auto record = [&](const LookupTuple& t) {
+        if (t.cols.empty() || t.cols.size() > (size_t)MS_JOIN_MAX_WIDTH || t.cols.size() != table_key.cols.size())
+            throw std::invalid_argument("join_rows: a key has 1 .. 4 columns, as many as the table key");
+        ms_lookup_tuple r = {{0, 0, 0, 0}, t.mask, t.mask_col, 0, 0};
+        for (size_t c = 0; c < t.cols.size(); c++) r.cols[c] = t.cols[c];
+        return r;
+    };
+    if (keys.size() > (size_t)MS_JOIN_MAX_SETS) throw std::invalid_argument("join_rows: at most 8 key sets in one call");
+    const ms_lookup_tuple trec = record(table_key);
+    std::vector<ms_lookup_tuple> krecs;
+    for (auto& t : keys) krecs.push_back(record(t));
+    std::vector<const void*> tin, in;
+    for (auto& c : table.columns) tin.push_back(c.ptr());
+    for (auto& c : base.columns) in.push_back(c.ptr());
+    const size_t n = base.num_rows();
+    JoinReport rep{{}, GpuVec<Fp>(pl, sizeof(ms_join_report) / 8)};
+    std::vector<void*> to;
+    for (size_t s = 0; s < keys.size(); s++) rep.matches.push_back(RowOrder{GpuVec<Fp>(pl, (n + 1) / 2), GpuVec<Fp>(pl, sizeof(ms_sort_report) / 8), n});
+    for (auto& m : rep.matches) to.push_back(m.index.ptr());
+    check(ms_join_rows(pl.ctx(), B::id, table.num_rows(), tin.data(), (unsigned)tin.size(), &trec, n, in.data(), (unsigned)in.size(),
+                       (unsigned)table_key.cols.size(), krecs.empty() ? nullptr : krecs.data(), (unsigned)krecs.size(), to.empty() ? nullptr : to.data(), rep.buf.ptr()));
+    return rep;
+}
+// The `payload` columns (indices into `table`) of the table row that holds each base row's key: join_rows for the one set `key`, then
+// permute_columns by the match; zero elements where the row is inactive or its key is not in the table.  -> (the columns, the join's report)
+template <class B>
+inline std::pair<Matrix<B>, JoinReport> fetch_columns(const Matrix<B>& table, const LookupTuple& table_key, const Matrix<B>& base, const LookupTuple& key,
+                                                      const std::vector<int>& payload) {
+    if (payload.empty()) throw std::invalid_argument("fetch_columns: no payload column");
+    Planner& pl = base.planner();
+    std::vector<const void*> in;
+    for (int c : payload) {
+        if (c < 0 || (size_t)c >= table.columns.size()) throw std::invalid_argument("fetch_columns: a payload column is an index into the table");
+        in.push_back(table.columns[c].ptr());
+    }
+    JoinReport rep = join_rows<B>(table, table_key, base, {key});
+    const size_t n = base.num_rows();
+    Matrix<B> out;
+    std::vector<void*> to;
+    for (size_t c = 0; c < in.size(); c++) out.columns.emplace_back(pl, n);
+    for (auto& c : out.columns) to.push_back(c.ptr());
+    check(ms_permute_columns(pl.ctx(), B::id, table.num_rows(), in.data(), to.data(), (unsigned)in.size(), rep.matches[0].index.ptr(), n));
+    return {std::move(out), std::move(rep)};
 }
 
 // A table whose row count differs from its source's, derived where the source lies (ms_gap_plan, ms_gap_fill): the rows the mask lets

@@ -136,7 +136,7 @@ int canon_col(ms_ctx* ctx, const char* entry, const char* arg, int field, size_t
 }
 // the columns of d_base a call names, over Fp or Fp252: only what the call reads is scanned (an output may be a column of d_base, of any
 // content), and the column reported is the caller's index, not the one in the table scanned
-int canon_named(ms_ctx* ctx, const char* entry, int field, size_t n, const void* const* d_base, const std::vector<unsigned>& used) {
+int canon_named(ms_ctx* ctx, const char* entry, int field, size_t n, const void* const* d_base, const std::vector<unsigned>& used, const char* arg) {
     if (!ctx || !ctx->checked || !n || used.empty()) return MS_OK;
     unsigned V = 0;
     if (field_words(field, &V) != MS_OK) return MS_OK;
@@ -147,7 +147,7 @@ int canon_named(ms_ctx* ctx, const char* entry, int field, size_t n, const void*
         std::lock_guard<std::mutex> lk(ctx->mu);
         MSCHK(scan_locked(ctx, V, n, tab.data(), (unsigned)tab.size(), &r));
     }
-    return r.count ? refuse(entry, "d_base", V, used[r.first_col], r.first_row, r.first_word) : MS_OK;
+    return r.count ? refuse(entry, arg, V, used[r.first_col], r.first_row, r.first_word) : MS_OK;
 }
 // a row-major matrix [nrows][ncols]: scanned as one run of nrows * ncols elements
 int canon_rows(ms_ctx* ctx, const char* entry, const char* arg, int field, size_t nrows, unsigned ncols, const void* d_matrix) {

@@ -1,5 +1,5 @@
 // Internal declarations shared by the translation units of libministark_hip.so (ms_core / ms_ntt / ms_stage / ms_hash / ms_eval / ms_deep /
-// ms_comm / ms_validate / ms_blake2s / ms_canon / ms_coin / ms_keccak / ms_ext / ms_logup / ms_rpo_coin / ms_lookup / ms_sort / ms_gaps .cpp,
+// ms_comm / ms_validate / ms_blake2s / ms_canon / ms_coin / ms_keccak / ms_ext / ms_logup / ms_rpo_coin / ms_lookup / ms_sort / ms_gaps / ms_join .cpp,
 // the SOURCES of build.py): the context, the plan object, error plumbing, pooled scratch, the checked mode's scans and the base-column
 // arguments of the trace-table entry points.  Not part of the C ABI.
 #pragma once
@@ -203,9 +203,9 @@ int canon_program(ms_ctx* ctx, const char* entry, bool is252, const uint32_t* h_
                   const void* const* d_ext_cols, unsigned next, const void* const* d_periodic, const unsigned* periodic_len, unsigned nperiodic);
 static inline int field_of_words(unsigned V) { return V == 1 ? MS_GOLDILOCKS_FP : V == 3 ? MS_GOLDILOCKS_FQ3 : MS_STARK252_FP; }
 // d_base[c] for c in `used` alone (what a call NAMES; the rest of d_base may hold anything); the refusal reports the caller's own column index
-int canon_named(ms_ctx* ctx, const char* entry, int field, size_t n, const void* const* d_base, const std::vector<unsigned>& used);
+int canon_named(ms_ctx* ctx, const char* entry, int field, size_t n, const void* const* d_base, const std::vector<unsigned>& used, const char* arg = "d_base");
 
-// ms_core.cpp: the base-column table (d_base, nbase) of a trace-table entry point (ms_ext / ms_logup / ms_lookup / ms_sort / ms_gaps .cpp):
+// ms_core.cpp: the base-column table (d_base, nbase) of a trace-table entry point (ms_ext / ms_logup / ms_lookup / ms_sort / ms_gaps / ms_join .cpp):
 // resolves the column indices of the caller's records to addresses, refuses the ones out of range, and keeps the list of the columns
 // named, in the order first named -- what the overlap checks and canon_named go through.  `what` / `who` open the refusal after
 // "<entry>: " and end in a space or in ": " ("key ", "lookup set 1: ", "column 3: term ").

@@ -24,12 +24,16 @@ Ordering rows -- a memory table by (address, cycle), the permuted columns of a p
 
 A table whose row count differs from its source's -- the rows a mask selects, a dummy row for every clock cycle missing between two rows of
 an address, padding up to the trace length -- is `gap_plan` over ms_gap_plan and `gap_fill` over ms_gap_fill
-(include/ministark_hip_gaps.h): the device decides the row count and writes the rows."""
+(include/ministark_hip_gaps.h): the device decides the row count and writes the rows.
+
+Fetching -- the instruction at an ip, the value at a ROM address, the result column of a function table -- is `join_rows` over ms_join_rows
+(include/ministark_hip_join.h): for every row, the index of the table row that holds its key, the table a matrix of its own; and
+`fetch_columns`, which hands that index to `permute_columns` and returns the table's other columns row by row."""
 import ctypes
 
 import numpy as np
 
-from ._lib import GapColumnRecord, GapReportRecord, GapSpecRecord, LookupReportRecord, LookupTupleRecord, SortKeyRecord, SortReportRecord
+from ._lib import GapColumnRecord, GapReportRecord, GapSpecRecord, JoinReportRecord, LookupReportRecord, LookupTupleRecord, SortKeyRecord, SortReportRecord
 from .api import FIELD_WORDS, GOLDILOCKS_FP, DeviceBytes, GpuVec, Matrix, _ptr_array, f252_from_mont_limbs, gl_from_mont
 
 MAX_TERMS, MAX_COLUMNS, NONE = 8, 32, -1
@@ -39,6 +43,7 @@ _MASK = {"nonzero": 1, "zero": 2}
 LOGUP_MAX_FRACTIONS, LOGUP_MAX_COLUMNS = 4, 32
 LOOKUP_MAX_WIDTH, LOOKUP_MAX_SETS = 4, 8
 SORT_MAX_KEYS, PERMUTE_MAX_COLUMNS = 4, 128
+JOIN_MAX_WIDTH, JOIN_MAX_SETS, JOIN_NONE = 4, 8, 0xFFFFFFFF
 
 
 def _mask_words(who, mask):
@@ -373,6 +378,105 @@ def permute_columns(planner, columns, index, n_out=None, out=None):
     L = planner.lib
     L.check(L.ms_permute_columns(planner.handle, field, n_src, _ptr_array(cols), _ptr_array(outs), len(cols), index.ptr, n_out))
     return Matrix(outs)
+
+
+class JoinReport:
+    """What `join_rows` found: the ms_join_report in device memory, downloaded (a host wait) when a field is first read.
+    .matched: active rows whose key the table holds; .missing: active rows whose key it does not; .first_missing_set / .first_missing_row:
+    the smallest (set, row) among them (0, 0 when there is none); .duplicate_table_rows: active table rows equal to an earlier one (no row
+    matches them); .table_active: the table rows its mask lets through."""
+
+    def __init__(self, planner, buf, cols, keys):
+        self.planner, self.buf, self._cols, self._keys, self._rec = planner, buf, cols, keys, None
+
+    def _read(self):
+        if self._rec is None:
+            rec = JoinReportRecord()
+            self.planner.lib.check(self.planner.lib.ms_download(self.planner.handle, ctypes.addressof(rec), self.buf.ptr, ctypes.sizeof(rec)))
+            self._rec = rec
+        return self._rec
+
+    matched = property(lambda self: int(self._read().matched))
+    missing = property(lambda self: int(self._read().missing))
+    first_missing_row = property(lambda self: int(self._read().first_missing_row))
+    first_missing_set = property(lambda self: int(self._read().first_missing_set))
+    duplicate_table_rows = property(lambda self: int(self._read().duplicate_table_rows))
+    table_active = property(lambda self: int(self._read().table_active))
+
+    def __bool__(self):
+        return self.missing == 0                 # true when every active row found its table row
+
+    def __repr__(self):
+        return (f"JoinReport(matched={self.matched}, missing={self.missing}, first_missing_set={self.first_missing_set}, "
+                f"first_missing_row={self.first_missing_row}, duplicate_table_rows={self.duplicate_table_rows}, table_active={self.table_active})")
+
+    def first_missing_values(self):
+        """the canonical values of the first missing key (it downloads those elements, nothing else), or None"""
+        if not self.missing:
+            return None
+        row, L = self.first_missing_row, self.planner.lib
+        vals = []
+        for c in self._keys[self.first_missing_set].cols:
+            col = self._cols[c]
+            V = FIELD_WORDS[col.field]
+            w = np.empty(V, dtype=np.uint64)
+            L.check(L.ms_download(self.planner.handle, w.ctypes.data, col.ptr + row * V * 8, V * 8))
+            vals.append(gl_from_mont(int(w[0])) if col.field == GOLDILOCKS_FP else f252_from_mont_limbs([int(x) for x in w]))
+        return vals
+
+    def check(self):
+        """raises LookupMissing, naming set, row and the key's values, when an active row's key is not in the table"""
+        if self.missing:
+            s, row, vals = self.first_missing_set, self.first_missing_row, self.first_missing_values()
+            err = LookupMissing(f"key set {s}, row {row}: the key ({', '.join(str(v) for v in vals)}) in base columns {self._keys[s].cols} "
+                                f"is not a row of the table; {self.missing} row(s) in all have no table row")
+            err.set, err.row, err.values, err.missing = s, row, vals, self.missing
+            raise err
+        return self
+
+
+def join_rows(planner, table, table_key, base, keys):
+    """-> (matches, report): matches[s][i] = the smallest active row of `table` whose key (`table_key`, a LookupTuple over `table`) equals
+    the key of row i of `base` under keys[s] (LookupTuples of that width over `base`), or JOIN_NONE for an inactive row and for a key the
+    table does not hold.  table, base: each a Matrix or a list of GpuVecs, of one length and one field, both of the same field (they may be
+    the same columns: a self-join).  matches: one DeviceIndex per set, which `permute_columns` reads as it is.  report: a JoinReport.
+    Enqueues and returns: no host wait until the report or an index is read."""
+    tcols = table.columns if isinstance(table, Matrix) else list(table)
+    cols = base.columns if isinstance(base, Matrix) else list(base)
+    keys = list(keys)
+    n_table, field = _same_columns("join_rows: table", tcols)
+    n, base_field = _same_columns("join_rows: base", cols)
+    if base_field != field:
+        raise ValueError("join_rows: the table and the base columns are of different fields")
+    if any(len(k.cols) != len(table_key.cols) for k in keys):
+        raise ValueError("join_rows: every key set has as many columns as the table key")
+    if len(keys) > JOIN_MAX_SETS:
+        raise ValueError(f"join_rows: at most {JOIN_MAX_SETS} key sets in one call, not {len(keys)}")
+    matches = [DeviceIndex(planner, n) for _ in keys]
+    buf = GpuVec(planner, ctypes.sizeof(JoinReportRecord) // 8, GOLDILOCKS_FP)
+    trec = np.array(table_key._record(), dtype=np.int32)
+    krec = np.array([k._record() for k in keys], dtype=np.int32).reshape(-1, 8)
+    assert trec.nbytes == ctypes.sizeof(LookupTupleRecord)
+    L = planner.lib
+    L.check(L.ms_join_rows(planner.handle, field, n_table, _ptr_array(tcols), len(tcols), trec.ctypes.data, n, _ptr_array(cols), len(cols),
+                           len(table_key.cols), krec.ctypes.data if krec.size else None, len(keys), _ptr_array(matches) if matches else None, buf.ptr))
+    return matches, JoinReport(planner, buf, cols, keys)
+
+
+def fetch_columns(planner, table, table_key, base, key, payload, out=None, check=False):
+    """-> (Matrix, report): for every row of `base`, the `payload` columns (indices into `table`) of the table row that holds its key:
+    `join_rows` for the one set `key`, then `permute_columns` by the match.  A row that is inactive or whose key the table does not hold
+    gets zero elements (the report counts the latter).  out: GpuVecs to fill, one per payload column, or None for new ones.  check: read the
+    report (a host wait) and raise LookupMissing if a key is missing."""
+    tcols = table.columns if isinstance(table, Matrix) else list(table)
+    payload = [int(c) for c in payload]
+    if not payload or any(not 0 <= c < len(tcols) for c in payload):
+        raise ValueError(f"fetch_columns: payload is a non-empty list of indices into the table's {len(tcols)} columns, not {payload!r}")
+    (match,), report = join_rows(planner, tcols, table_key, base, [key])
+    fetched = permute_columns(planner, [tcols[c] for c in payload], match, out=out)
+    if check:
+        report.check()
+    return fetched, report
 
 
 GAP_MAX_GROUP, GAP_MAX_COLUMNS = 3, 128

@@ -225,6 +225,53 @@ def lookup_trace_on_device(planner, n, seed, check=False):
     return trace
 
 
+def fetch_program(n, seed):
+    """The program table of `fetch_trace`: L = n / 2 rows (addr, val) as canonical integers, the addresses an affine progression mod p with
+    a nonzero step -- distinct by construction -- and the values drawn."""
+    assert n >= 4
+    rng = np.random.default_rng([seed, 1])
+    start, step = (int(v) for v in rng.integers(1, GL_P, size=2, dtype=np.uint64))
+    L = n // 2
+    return [[(start + j * step) % GL_P for j in range(L)], [int(v) for v in rng.integers(0, GL_P, size=L, dtype=np.uint64)]]
+
+
+def fetch_trace(n, seed, program=None):
+    """A valid base trace of `lookup_air` whose looked-up VALUES are fetched: columns a0, a1, t0, t1, m as canonical integers.  The program
+    (`fetch_program(n, seed)` unless one is given) is a table of n / 2 rows (addr, val) with distinct addresses; t0, t1 are the program
+    padded to n rows by repeating its last row (the repeated rows are duplicates of it: m = 0); a0 is n addresses drawn from the program,
+    a1[i] the value the program holds at a0[i] -- an instruction fetch -- and m[j] counts the rows that read program row j."""
+    addr, val = fetch_program(n, seed) if program is None else program
+    L = len(addr)
+    rng = np.random.default_rng([seed, 2])
+    idx = [int(v) for v in rng.integers(0, L, size=n)]
+    m = [0] * n
+    for j in idx:
+        m[j] += 1
+    pad = lambda c: list(c) + [c[-1]] * (n - L)
+    return [[addr[j] for j in idx], [val[j] for j in idx], pad(addr), pad(val), m]
+
+
+def fetch_trace_on_device(planner, n, seed, check=False, a0=None):
+    """`fetch_trace(n, seed)` built where the trace lies: a0, the program and t0, t1 are uploaded; a1 is FETCHED -- ms_join_rows finds, for
+    every a0[i], the program row that holds that address and ms_permute_columns reads its value (extension.fetch_columns, into the trace's
+    own a1 column) -- and ms_lookup_multiplicities fills m in place.  Nothing is downloaded.
+    -> the base trace as a Matrix of five Fp columns, equal to the uploaded `fetch_trace` in every word.  check: read both calls' reports
+    (host waits) and raise LookupMissing if an address is not in the program, or a looked-up pair is not a row of the table.
+    a0: the addresses to fetch, in place of the drawn ones (canonical integers)."""
+    from .extension import LookupTuple, fetch_columns, lookup_multiplicities
+    program = fetch_program(n, seed)
+    cols = fetch_trace(n, seed, program)
+    words = lambda c: to_mont_words(GOLDILOCKS_FP, c).ravel()
+    zero = np.zeros(n, dtype=np.uint64)
+    d_program = Matrix.from_numpy(planner, [words(c) for c in program], GOLDILOCKS_FP)
+    trace = Matrix.from_numpy(planner, [words(cols[0] if a0 is None else a0), zero, words(cols[2]), words(cols[3]), zero], GOLDILOCKS_FP)
+    fetch_columns(planner, d_program, LookupTuple([0]), trace, LookupTuple([0]), [1], out=[trace.columns[1]], check=check)
+    _, report = lookup_multiplicities(planner, trace, LookupTuple([2, 3]), [LookupTuple([0, 1])], out=trace.columns[4])
+    if check:
+        report.check()
+    return trace
+
+
 def lookup_air_constraints(n):
     """The two constraints of `lookup_air`, in its order: the boundary S = 0 at row 0, and the transition over the full zerofier X^n - 1."""
     x = E.X()

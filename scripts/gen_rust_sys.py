@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generate rust/gpu/src/hip/sys.rs -- the raw `extern "C"` bindings of the reference-side shim -- from
-include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h and sys_gaps.rs from include/ministark_hip_gaps.h.  tests/test_rust_shim.py re-runs the parser and
+include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h, sys_gaps.rs from include/ministark_hip_gaps.h and sys_join.rs from include/ministark_hip_join.h.  tests/test_rust_shim.py re-runs the parser and
 checks the committed file against the header, which stands in for compiling it (no Rust toolchain in the image).
 
     python scripts/gen_rust_sys.py            # rewrite rust/gpu/src/hip/sys.rs
@@ -28,6 +28,8 @@ SORT_HEADER = os.path.join(ROOT, "include", "ministark_hip_sort.h")
 SORT_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_sort.rs")
 GAPS_HEADER = os.path.join(ROOT, "include", "ministark_hip_gaps.h")
 GAPS_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_gaps.rs")
+JOIN_HEADER = os.path.join(ROOT, "include", "ministark_hip_join.h")
+JOIN_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_join.rs")
 
 BASE = {"int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "long": "c_long", "size_t": "usize", "uint64_t": "u64",
         "uint32_t": "u32", "char": "c_char", "unsigned char": "u8", "void": "c_void", "ms_ctx": "ms_ctx", "ms_ntt_plan": "ms_ntt_plan", "ms_xchg_op": "ms_xchg_op", "ms_p2p_op": "ms_p2p_op", "ms_jit_stats": "ms_jit_stats"}
@@ -339,6 +341,32 @@ def gaps_prototypes():
     return prototypes(text[text.index("#define MINISTARK_HIP_GAPS_H"):])
 
 
+def render_join(protos):
+    """sys_join.rs: the entry point of include/ministark_hip_join.h (rows joined against a table: the matched row index), on sys.rs's types;
+    the key record is sys_lookup.rs's ms_lookup_tuple and the mask kinds are sys_ext.rs's"""
+    lines = ["// GENERATED by scripts/gen_rust_sys.py from include/ministark_hip_join.h -- do not edit by hand.",
+             "// Raw bindings of the row-join layer of libministark_hip.so (INTEGRATION.md section 3e); ms_lookup_tuple: sys_lookup.rs; the MS_EXT_* mask kinds: sys_ext.rs.",
+             "#![allow(non_camel_case_types)]",
+             "use core::ffi::{c_int, c_uint, c_void};",
+             "use super::sys::ms_ctx;",
+             "",
+             "#[repr(C)] #[derive(Clone, Copy, Debug, Default)] pub struct ms_join_report { pub matched: u64, pub missing: u64, pub first_missing_row: u64, pub first_missing_set: u32, pub pad: u32, pub duplicate_table_rows: u64, pub table_active: u64 }",
+             ] + [f"pub const {name}: c_int = {value};" for name, value in header_enums(JOIN_HEADER)] + [
+             "pub const MS_JOIN_NONE: u32 = 0xFFFFFFFF;",
+             "",
+             '#[link(name = "ministark_hip")]', 'extern "C" {']
+    for name, ret, plist in protos:
+        args = ", ".join(f"{(p + '_') if p in RUST_KEYWORDS else p}: {t}" for p, t in plist)
+        lines.append(f"    pub fn {name}({args})" + (f" -> {ret};" if ret else ";"))
+    lines += ["}", ""]
+    return "\n".join(lines)
+
+
+def join_prototypes():
+    text = open(JOIN_HEADER).read()
+    return prototypes(text[text.index("#define MINISTARK_HIP_JOIN_H"):])
+
+
 def main():
     protos = prototypes(open(HEADER).read())
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
@@ -377,6 +405,10 @@ def main():
     with open(GAPS_OUT, "w") as f:
         f.write(render_gaps(protos))
     print(f"{len(protos)} prototypes -> {GAPS_OUT}")
+    protos = join_prototypes()
+    with open(JOIN_OUT, "w") as f:
+        f.write(render_join(protos))
+    print(f"{len(protos)} prototypes -> {JOIN_OUT}")
 
 
 if __name__ == "__main__":
