@@ -459,7 +459,12 @@ int ms_sha256_pow_grind(ms_ctx* ctx, const void* h_seed32, unsigned bits, uint64
  *                             the reference's padding rule when ncols is not a multiple of 8
  * ms_rpo256_rows_row_major  = the same for a row-major matrix [nrows][ncols] (GpuRpo256RowMajor: ncols = 8)
  * ms_rpo256_merkle          = gen_rpo_merkle_tree: nodes[k] = merge(nodes[2k], nodes[2k+1]), leaf pairs feed
- *                             nodes[n/2 ..), nodes[1] = root, nodes[0] = zero */
+ *                             nodes[n/2 ..), nodes[1] = root, nodes[0] = zero
+ * Refused before anything is enqueued: a null ctx, d_cols, d_matrix, d_leaves, d_digests or d_nodes and a null
+ * d_cols[c] (ms_rpo256_rows and ms_rpo256_rows_field alike: "null column <c>") with MS_ERR_INVALID, as is
+ * ncols = 0 and a leaf count that is no power of two >= 2; more than 128 absorbed words per row (129 Fp
+ * columns, 43 Fq3 columns) and a field that is not Goldilocks with MS_ERR_UNSUPPORTED.  nrows = 0 is MS_OK
+ * and writes nothing. */
 int ms_rpo256_rows(ms_ctx* ctx, size_t nrows, const void* const* d_cols, unsigned ncols, void* d_digests);
 int ms_rpo256_rows_row_major(ms_ctx* ctx, size_t nrows, unsigned ncols, const void* d_matrix, void* d_digests);
 /* MatrixMerkleTree over RPO-256 (README.md:90 "coming soon"): the leaf of row r absorbs the

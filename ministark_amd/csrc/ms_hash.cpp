@@ -65,7 +65,10 @@ extern "C" int ms_rpo256_rows(ms_ctx* ctx, size_t nrows, const void* const* d_co
     if (!ctx || !d_cols || !d_digests) return fail(MS_ERR_INVALID, "ms_rpo256_rows: null argument");
     if (ncols && ncols <= (unsigned)msrpo::MAXCOLS) MSCHK(canon_cols(ctx, "ms_rpo256_rows", "d_cols", MS_GOLDILOCKS_FP, nrows, d_cols, ncols));
     std::vector<const uint64_t*> cols(ncols);
-    for (unsigned c = 0; c < ncols; c++) cols[c] = (const uint64_t*)d_cols[c];
+    for (unsigned c = 0; c < ncols; c++) {
+        if (!d_cols[c]) return fail(MS_ERR_INVALID, "null column %u", c);        // (canon_cols scans nothing when a column is null)
+        cols[c] = (const uint64_t*)d_cols[c];
+    }
     return rpo_rows(ctx, nrows, cols.data(), ncols, 1, d_digests);
 }
 // rows of a column-major matrix of `field`: an Fq3 column contributes its components c0, c1, c2 in the order

@@ -1,7 +1,8 @@
 // TEST INFRASTRUCTURE ONLY -- the field primitives one at a time, for tests/test_field_primitives.py.
 //
 // One kernel per header (gl.h, gl_dev.h, gl_limb.h, the accumulators of eval_kernels.h, fp252.h); `op` picks the primitive and
-// its template arguments.  Case i reads in[i * is ..] and writes every word of its result to out[i * os ..]: weak residues, raw
+// its template arguments.  The RPO-256 permutation (rpo_kernels.h, rpo_coin_kernels.h) has one lane-per-case kernel for its pieces,
+// two kernels that hold a state across lanes as the wide forms do, and one entry that runs the whole permutation in every form.  Case i reads in[i * is ..] and writes every word of its result to out[i * os ..]: weak residues, raw
 // limbs and raw accumulator columns as they are, so that the device build can be compared word for word with the host build.
 //
 // Built twice by tests/prim/prims.py: by hipcc for gfx950 (the inline assembly, builtins and constant-address-space loads of the
@@ -17,6 +18,10 @@
 #include "fp252.h"
 #include "eval_kernels.h"
 #include "ntt2_kernels.h"
+#include "rpo_kernels.h"
+#include "rpo_coin_kernels.h"
+#include <string.h>
+#include <vector>
 
 typedef uint64_t u64;
 static constexpr int BLOCK = 64;
@@ -305,10 +310,94 @@ __global__ void __launch_bounds__(BLOCK) k_f252(KARGS) {
     (void)aux; (void)tab; (void)ntab;
 }
 
+// ---- rpo_kernels.h, rpo_coin_kernels.h: the pieces of the RPO-256 permutation ---------------------------------------------------
+// One lane per case.  op: 0 apply_mds (12 words), 1 pow7, 2 pow_inv7 (one word), 3 pow_inv7_all (12 words, then the twelve pow_inv7
+//     of the same words), 4 pow7(gl::add(s[j], RC0[12 aux + j])), 5 pow_inv7(gl::add(s[j], RC1[12 aux + j])) for j < 12: the two
+//     S-box layers of round aux as msrpo::permute and the wide forms write them
+__global__ void __launch_bounds__(BLOCK) k_rpo(KARGS) {
+    CASE_PTRS
+    msrpo::State st;
+    #pragma unroll
+    for (int j = 0; j < 12; j++) st.s[j] = is >= 12 ? a[j] : 0;
+    switch (op) {
+    case 0:
+        msrpo::apply_mds(st);
+        #pragma unroll
+        for (int j = 0; j < 12; j++) o[j] = st.s[j];
+        break;
+    case 1: o[0] = msrpo::pow7(a[0]); break;
+    case 2: o[0] = msrpo::pow_inv7(a[0]); break;
+    case 3:
+        #pragma unroll
+        for (int j = 0; j < 12; j++) o[12 + j] = msrpo::pow_inv7(st.s[j]);
+        msrpo::pow_inv7_all(st.s);
+        #pragma unroll
+        for (int j = 0; j < 12; j++) o[j] = st.s[j];
+        break;
+    case 4:
+        #pragma unroll
+        for (int j = 0; j < 12; j++) o[j] = msrpo::pow7(gl::add(st.s[j], msrpo::RC0[aux * 12 + j]));
+        break;
+    case 5:
+        #pragma unroll
+        for (int j = 0; j < 12; j++) o[j] = msrpo::pow_inv7(gl::add(st.s[j], msrpo::RC1[aux * 12 + j]));
+        break;
+    default: break;
+    }
+    (void)tab; (void)ntab;
+}
+// op 100: msrpo::mds_wide as rpo256_merge_level_wide holds a state -- sixteen lanes per case, four cases per block of 64, lane j < 12
+// of a group owns element j, the four spare lanes shadow elements 0..3.  Words 0..12 of a case: mds_wide; words 12..24: apply_mds
+// on the same state, by the group's first lane.  Every lane reaches both barriers.
+__global__ void __launch_bounds__(BLOCK) k_rpo_mds16(KARGS) {
+    __shared__ u64 sh_all[BLOCK / 16][12];
+    const unsigned g = threadIdx.x / 16, j16 = threadIdx.x % 16;
+    const bool owner = j16 < 12;
+    const unsigned j = owner ? j16 : j16 - 12;
+    const size_t i = (size_t)blockIdx.x * (BLOCK / 16) + g;
+    const bool live = i < (size_t)n;
+    uint32_t row[12];
+    #pragma unroll
+    for (int q = 0; q < 12; q++) row[q] = msrpo::MDS_ROW[(q + 12 - j) % 12];
+    u64 s = live ? in[i * is + j] : 0;
+    s = msrpo::mds_wide(s, sh_all[g], j, owner, row);
+    if (live && owner) out[i * os + j] = s;
+    if (live && j16 == 0) {
+        msrpo::State st;
+        #pragma unroll
+        for (int q = 0; q < 12; q++) st.s[q] = in[i * is + q];
+        msrpo::apply_mds(st);
+        #pragma unroll
+        for (int q = 0; q < 12; q++) out[i * os + 12 + q] = st.s[q];
+    }
+    (void)op; (void)aux; (void)tab; (void)ntab;
+}
+// op 101: msrpo::mds_wide as the coin holds a state -- msrpocoin::Wide, one case (a 16-word state record) per block of 64, lanes
+// 12..63 shadow; the record written back carries pos = 4 in word 12
+__global__ void __launch_bounds__(BLOCK) k_rpo_mds_coin(KARGS) {
+    __shared__ u64 sh[12];
+    msrpocoin::Wide sp;
+    sp.load((const msrpocoin::State*)(in + (size_t)blockIdx.x * is), sh);
+    sp.s = msrpo::mds_wide(sp.s, sp.sh, sp.j, sp.owner, sp.row);
+    sp.store((msrpocoin::State*)(out + (size_t)blockIdx.x * os), 4);
+    (void)op; (void)aux; (void)n; (void)tab; (void)ntab;
+}
+// op 200, first part: msrpo::permute called directly, one lane per case; words 0..12
+__global__ void __launch_bounds__(BLOCK) k_rpo_permute(KARGS) {
+    CASE_PTRS
+    msrpo::State st;
+    #pragma unroll
+    for (int j = 0; j < 12; j++) st.s[j] = a[j];
+    msrpo::permute(st);
+    #pragma unroll
+    for (int j = 0; j < 12; j++) o[j] = st.s[j];
+    (void)op; (void)aux; (void)tab; (void)ntab;
+}
+
 // ---- host entries: allocate, upload, launch, synchronise, download.  0 = success; a failing step returns its line, never aborts.
 #define TRY(x) do { if (rc == 0 && (x) != hipSuccess) rc = __LINE__; } while (0)
 template <class K>
-static int run(K kern, int op, int aux, const u64* in, int is, u64* out, int os, int n, const u64* tab, int ntab) {
+static int run(K kern, int op, int aux, const u64* in, int is, u64* out, int os, int n, const u64* tab, int ntab, int per_block = BLOCK) {
     if (n <= 0 || is <= 0 || os <= 0 || ntab < 0) return -1;
     const size_t nin = (size_t)n * is, nout = (size_t)n * os, nt = ntab > 0 ? (size_t)ntab : 1;
     u64 *din = nullptr, *dout = nullptr, *dtab = nullptr;
@@ -321,7 +410,7 @@ static int run(K kern, int op, int aux, const u64* in, int is, u64* out, int os,
     TRY(hipMemset(dtab, 0, nt * 8));
     if (ntab > 0) TRY(hipMemcpy(dtab, tab, (size_t)ntab * 8, hipMemcpyHostToDevice));
     if (rc == 0) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, 0, op, aux, din, is, dout, os, n, dtab, ntab);
+        hipLaunchKernelGGL(kern, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(BLOCK), 0, 0, op, aux, din, is, dout, os, n, dtab, ntab);
         TRY(hipGetLastError());
     }
     TRY(hipDeviceSynchronize());
@@ -330,6 +419,83 @@ static int run(K kern, int op, int aux, const u64* in, int is, u64* out, int os,
     if (dout) (void)hipFree(dout);
     if (dtab) (void)hipFree(dtab);
     return rc;
+}
+
+// rpo op 200: the whole permutation in every device form, on the same n states of 12 words.  42 words per case:
+//    0..12  msrpo::permute, called directly (k_rpo_permute)
+//   12..24  the coin's Wide form: rpo_coin_step<Wide, OP_CREATE> launched as ms_rpo_coin.cpp launches it (one block of one wave) on a
+//           state record that holds the state with nothing unread (pos = 12); word 40 = the record's pos afterwards (4)
+//   24..36  the same with the coin's Narrow form; word 41 = pos
+//   36..40  rpo256_merge_level_wide itself, launched as ms_rpo256_merkle launches it (64 threads, four nodes per workgroup), on the
+//           rate words 4..12 of the state: its capacity is zero by construction
+template <class SP>
+static int run_coin_permute(const u64* in, u64* out, int os, int n, int at, int pos_at) {
+    std::vector<msrpocoin::State> recs((size_t)n);
+    memset(recs.data(), 0, recs.size() * sizeof(msrpocoin::State));
+    for (int i = 0; i < n; i++) {
+        for (int j = 0; j < 12; j++) recs[i].s[j] = in[(size_t)i * 12 + j];
+        recs[i].pos = 12;
+    }
+    msrpocoin::State* d = nullptr;
+    int rc = 0;
+    TRY(hipMalloc((void**)&d, recs.size() * sizeof(msrpocoin::State)));
+    TRY(hipMemcpy(d, recs.data(), recs.size() * sizeof(msrpocoin::State), hipMemcpyHostToDevice));
+    for (int i = 0; i < n && rc == 0; i++) {
+        hipLaunchKernelGGL((msrpocoin::rpo_coin_step<SP, msrpocoin::OP_CREATE>), dim3(1), dim3(msrpocoin::WAVE), 0, 0, d + i, (const u64*)nullptr, (u64)0,
+                           (size_t)0, (u64*)nullptr);
+        TRY(hipGetLastError());
+    }
+    TRY(hipDeviceSynchronize());
+    TRY(hipMemcpy(recs.data(), d, recs.size() * sizeof(msrpocoin::State), hipMemcpyDeviceToHost));
+    if (d) (void)hipFree(d);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) {
+        for (int j = 0; j < 12; j++) out[(size_t)i * os + at + j] = recs[i].s[j];
+        out[(size_t)i * os + pos_at] = recs[i].pos;
+    }
+    return 0;
+}
+static int run_permute_forms(const u64* in, int is, u64* out, int os, int n) {
+    if (n <= 0 || is != 12 || os != 42) return -1;
+    std::vector<u64> tmp((size_t)n * 12);
+    int rc = run(k_rpo_permute, 200, 0, in, 12, tmp.data(), 12, n, nullptr, 0);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < 12; j++) out[(size_t)i * os + j] = tmp[(size_t)i * 12 + j];
+    if ((rc = run_coin_permute<msrpocoin::Wide>(in, out, os, n, 12, 40)) != 0) return rc;
+    if ((rc = run_coin_permute<msrpocoin::Narrow>(in, out, os, n, 24, 41)) != 0) return rc;
+    std::vector<u64> src((size_t)n * 8), dig((size_t)n * 4);
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < 8; j++) src[(size_t)i * 8 + j] = in[(size_t)i * 12 + 4 + j];
+    u64 *dsrc = nullptr, *ddst = nullptr;
+    TRY(hipMalloc((void**)&dsrc, src.size() * 8));
+    TRY(hipMalloc((void**)&ddst, dig.size() * 8));
+    TRY(hipMemcpy(dsrc, src.data(), src.size() * 8, hipMemcpyHostToDevice));
+    TRY(hipMemset(ddst, 0, dig.size() * 8));
+    if (rc == 0) {
+        hipLaunchKernelGGL(msrpo::rpo256_merge_level_wide, dim3((unsigned)((n + 3) / 4)), dim3(msrpo::NTW), 0, 0, (const u64*)dsrc, ddst, (size_t)n);
+        TRY(hipGetLastError());
+    }
+    TRY(hipDeviceSynchronize());
+    TRY(hipMemcpy(dig.data(), ddst, dig.size() * 8, hipMemcpyDeviceToHost));
+    if (dsrc) (void)hipFree(dsrc);
+    if (ddst) (void)hipFree(ddst);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < 4; j++) out[(size_t)i * os + 36 + j] = dig[(size_t)i * 4 + j];
+    return 0;
+}
+extern "C" int fp_rpo(int op, int aux, const u64* in, int is, u64* out, int os, int n, const u64* tab, int ntab) {
+    switch (op) {                                       // every kernel indexes a case by these widths: refuse any other
+    case 0: return is == 12 && os == 12 ? run(k_rpo, op, aux, in, is, out, os, n, tab, ntab) : -1;
+    case 1: case 2: return is == 1 && os == 1 ? run(k_rpo, op, aux, in, is, out, os, n, tab, ntab) : -1;
+    case 3: return is == 12 && os == 24 ? run(k_rpo, op, aux, in, is, out, os, n, tab, ntab) : -1;
+    case 4: case 5: return is == 12 && os == 12 && aux >= 0 && aux < 7 ? run(k_rpo, op, aux, in, is, out, os, n, tab, ntab) : -1;
+    case 100: return is == 12 && os == 24 ? run(k_rpo_mds16, op, aux, in, is, out, os, n, tab, ntab, BLOCK / 16) : -1;
+    case 101: return is == 16 && os == 16 ? run(k_rpo_mds_coin, op, aux, in, is, out, os, n, tab, ntab, 1) : -1;
+    case 200: return run_permute_forms(in, is, out, os, n);
+    default: return -1;
+    }
 }
 #undef TRY
 

@@ -4,7 +4,8 @@ tests/prim/field_prims.hip is built twice -- by hipcc for gfx950 (the inline ass
 the device branches) and by g++ against the simulator of tests/emu (the #else branches) -- and both run the same inputs.  Inputs are
 drawn per edge class: one class per branch or fix-up of a primitive, plus uniform inputs and edge values crossed pairwise.  Every
 class asserts its defining condition on each input it keeps, so a generator bug cannot leave a class empty or off target.  Expected
-values are Python integers computed from the contract in each primitive's header comment, never from either build.
+values are Python integers computed from the contract in each primitive's header comment, never from either build; the pieces of
+the RPO-256 permutation (family "rpo") are checked against oracle/pyref/rpo.py.
 
     python tests/prim/prims.py device LIB.so IN.npz OUT.npz    # every op of IN on one build, one process, stops at the first failure
 """
@@ -22,9 +23,12 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "ministark_amd", "csrc")
 EMU = os.path.join(ROOT, "tests", "emu")
 SRC = os.path.join(HERE, "field_prims.hip")
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from oracle.pyref import rpo as pyrpo  # noqa: E402    (the reference of the rpo family)
 OUT = os.path.join(EMU, "_build")                  # git-ignored
 BLOCK = 64                                         # lanes per block in field_prims.hip: pool and twiddle slots are per block
-FAMILIES = ["gl", "gld", "limb", "acc", "f252"]
+FAMILIES = ["gl", "gld", "limb", "acc", "f252", "rpo"]
 
 
 # ---- building ------------------------------------------------------------------------------------------------------------------
@@ -895,7 +899,131 @@ def _f252(n):
     return ops
 
 
-_BUILDERS = {"gl": _gl, "gld": _gld, "limb": _limb, "acc": _acc, "f252": _f252}
+# rpo_kernels.h, rpo_coin_kernels.h: the pieces of the RPO-256 permutation and the permutation in every device form.  The reference
+# is oracle/pyref/rpo.py (Python integers on canonical values, pinned to external vectors by tests/test_rpo_parity.py); the device
+# holds Montgomery words w = x 2^64 mod p, so a word goes through _val on its way in and through _word on its way out.  The MDS
+# accumulator sees the words themselves: its classes are conditions on the integer sum of words.
+E8 = [0, 1, P - 1, P - 2, M32, 1 << 32, (1 << 32) + 1, P - (1 << 32)]
+assert all(e < P for e in E8)
+UNITY_ORDERS = [2, 3, 4, 5, 8, 15, 16, 17, 257, 65537, 1 << 32]
+assert all((P - 1) % d == 0 for d in UNITY_ORDERS)
+# x^7 = 1 has no solution but x = 1: 7 does not divide p - 1, which is what makes x^7 a permutation.  In place of that (empty) class
+# the S-boxes get elements of small order, whose squaring chains run through 1 and p - 1.
+assert (P - 1) % 7 != 0
+
+
+def _val(w): return w * RINV % P
+def _word(x): return (x << 64) % P
+def _vals(ws): return [_val(w) for w in ws]
+def _words(xs): return [_word(x) for x in xs]
+def _mds_sums(ws): return [sum(pyrpo.MDS_ROW[(k - m) % 12] * ws[k] for k in range(12)) for m in range(12)]
+def _state(r): return [canon(r) for _ in range(12)]
+def _edge_state(r): return [r.choice(E8) for _ in range(12)]
+
+
+def _tag(name, msg):
+    return "%s: %s" % (name, msg) if msg else None
+
+
+def _rpo(n):
+    ops = []
+    n1, nm, np_ = 16 * n, 4 * n, max(2, n // 2)    # cases per class: one-element ops, MDS ops, whole permutations
+
+    def op(name, code, is_, os_, check, aux=0):
+        ops.append(Op("rpo", name, code, is_, os_, check, aux))
+        return ops[-1]
+
+    # ---- the MDS layer: sum_k MDS[m][k] s[k] as one integer below 160 2^64, reduced once
+    def mds_want(a):
+        return _words(pyrpo.apply_mds(_vals(a[:12])))
+
+    def solved(target):
+        """eleven words drawn, the twelfth solved for: row i mod 12 sums to `target` mod p"""
+        def make(r, i):
+            m, k = i % 12, r.randrange(12)
+            s = _state(r)
+            s[k] = 0
+            s[k] = (target - _mds_sums(s)[m]) * pow(pyrpo.MDS_ROW[(k - m) % 12], -1, P) % P
+            return s
+        return make
+
+    def mds_classes(o):
+        o.add("each edge value", [[e] * 12 for e in E8], lambda a, i: len(set(a)) == 1 and a[0] in E8)
+        o.gen("edge values crossed", nm, lambda r, i: _edge_state(r), lambda a, i: all(w in E8 for w in a))
+        o.add("all p-1: the largest sum", [[P - 1] * 12], lambda a, i: all(s == 160 * (P - 1) for s in _mds_sums(a)))
+        o.add("all zero", [[0] * 12], lambda a, i: not any(_mds_sums(a)))
+        o.gen("sum = k p, k > 0", nm, solved(0), lambda a, i: _mds_sums(a)[i % 12] > 0 and _mds_sums(a)[i % 12] % P == 0)
+        o.gen("sum = k p - 1", nm, solved(P - 1), lambda a, i: _mds_sums(a)[i % 12] % P == P - 1)
+        o.gen("high word 0", nm, lambda r, i: [r.getrandbits(r.randrange(1, 57)) for _ in range(12)],
+              lambda a, i: all(s >> 64 == 0 for s in _mds_sums(a)))
+        o.gen("high word 159", nm, lambda r, i: [P - 1 - r.getrandbits(r.randrange(1, 57)) for _ in range(12)],
+              lambda a, i: all(s >> 64 == 159 for s in _mds_sums(a)))
+        o.gen("uniform", nm, lambda r, i: _state(r), lambda a, i: all(w < P for w in a))
+
+    mds_classes(op("apply_mds", 0, 12, 12, lambda a, o, i: _eq(o[:12], mds_want(a))))
+    mds_classes(op("mds_wide (sixteen lanes) + apply_mds", 100, 12, 24,
+                   lambda a, o, i: _all(_tag("mds_wide", _eq(o[:12], mds_want(a))), _tag("apply_mds", _eq(o[12:24], mds_want(a))))))
+    mds_classes(op("mds_wide (coin Wide)", 101, 16, 16,
+                   lambda a, o, i: _all(_eq(o[:12], mds_want(a)), _tag("pos and pad", _eq(o[12:], [4, 0, 0, 0])))))
+
+    # ---- the S-boxes on one element
+    def sbox_classes(o, e):
+        o.add("word edges", [[w] for w in EC], lambda a, i: a[0] < P)
+        o.add("fixed points 0, 1, p-1", [[_word(x)] for x in (0, 1, P - 1)], lambda a, i, e=e: _val(a[0]) in (0, 1, P - 1) and pow(_val(a[0]), e, P) == _val(a[0]))
+        o.gen("small order", n1, lambda r, i: [_word(pow(7, (P - 1) // d * r.randrange(1, d), P)) for d in [r.choice(UNITY_ORDERS)]],
+              lambda a, i: _val(a[0]) != 1 and any(pow(_val(a[0]), d, P) == 1 for d in UNITY_ORDERS))
+        o.gen("uniform", n1, lambda r, i: [canon(r)], lambda a, i: a[0] < P)
+
+    sbox_classes(op("pow7", 1, 1, 1, lambda a, o, i: _eq(o[:1], [_word(pow(_val(a[0]), 7, P))])), 7)
+    sbox_classes(op("pow_inv7", 2, 1, 1, lambda a, o, i: _eq(o[:1], [_word(pow(_val(a[0]), pyrpo.INV7, P))])), pyrpo.INV7)
+
+    def inv7_all(a, o, i):
+        want = [_word(pow(x, pyrpo.INV7, P)) for x in _vals(a[:12])]
+        return _all(_tag("pow_inv7_all", _eq(o[:12], want)), _tag("twelve pow_inv7", _eq(o[12:24], want)))
+    o = op("pow_inv7_all", 3, 12, 24, inv7_all)
+    o.add("each edge value", [[e] * 12 for e in E8], lambda a, i: len(set(a)) == 1 and a[0] in E8)
+    o.gen("edge values crossed", nm, lambda r, i: _edge_state(r), lambda a, i: all(w in E8 for w in a))
+    o.gen("fixed points crossed", nm, lambda r, i: [_word(r.choice((0, 1, P - 1))) for _ in range(12)],
+          lambda a, i: all(x in (0, 1, P - 1) for x in _vals(a)))
+    o.gen("uniform", nm, lambda r, i: _state(r), lambda a, i: all(w < P for w in a))
+
+    # ---- gl::add(s, RC) and the S-box behind it, as the rounds use them: the twelve lanes of round r
+    assert all(c >= 1 << 32 for c in pyrpo.RC0_MONT + pyrpo.RC1_MONT)       # so that every class below exists for every constant
+    for kind, code, rc_words, rc_vals, e in (("rc0+pow7", 4, pyrpo.RC0_MONT, pyrpo.RC0, 7), ("rc1+pow_inv7", 5, pyrpo.RC1_MONT, pyrpo.RC1, pyrpo.INV7)):
+        for rnd in range(7):
+            rc, rv = rc_words[12 * rnd:12 * rnd + 12], rc_vals[12 * rnd:12 * rnd + 12]
+            o = op("%s[round %d]" % (kind, rnd), code, 12, 12,
+                   lambda a, o, i, rv=rv, e=e: _eq(o[:12], [_word(pow((x + c) % P, e, P)) for x, c in zip(_vals(a[:12]), rv)]), aux=rnd)
+            o.add("s + RC = p", [[P - c for c in rc]], lambda a, i, rc=rc: all(s + c == P for s, c in zip(a, rc)))
+            o.add("s + RC = p - 1", [[P - 1 - c for c in rc]], lambda a, i, rc=rc: all(s + c == P - 1 for s, c in zip(a, rc)))
+            o.gen("s + RC wraps 2^64", n, lambda r, i, rc=rc: [r.randrange((1 << 64) - c, P) for c in rc],
+                  lambda a, i, rc=rc: all(s < P and s + c > M64 for s, c in zip(a, rc)))
+            o.gen("p <= s + RC < 2^64", n, lambda r, i, rc=rc: [r.randrange(P - c, (1 << 64) - c) for c in rc],
+                  lambda a, i, rc=rc: all(s < P and P <= s + c <= M64 for s, c in zip(a, rc)))
+            o.gen("s + RC < p", n, lambda r, i, rc=rc: [r.randrange(P - c) for c in rc], lambda a, i, rc=rc: all(s + c < P for s, c in zip(a, rc)))
+            o.gen("edge values crossed", n, lambda r, i: _edge_state(r), lambda a, i: all(w in E8 for w in a))
+
+    # ---- the whole permutation in every device form (field_prims.hip, op 200), on full 12-element states
+    def forms(a, o, i):
+        a = a[:12]
+        want = _words(pyrpo.permute(_vals(a)))
+        want0 = want[4:8] if not any(a[:4]) else _words(pyrpo.permute([0] * 4 + _vals(a[4:])))[4:8]
+        return _all(_tag("msrpo::permute", _eq(o[0:12], want)), _tag("coin Wide", _eq(o[12:24], want)), _tag("coin Narrow", _eq(o[24:36], want)),
+                    _tag("rpo256_merge_level_wide on the rate words", _eq(o[36:40], want0)), _tag("pos after Wide, Narrow", _eq(o[40:42], [4, 4])),
+                    _tag("Wide against msrpo::permute", _eq(o[12:24], o[0:12])), _tag("Narrow against msrpo::permute", _eq(o[24:36], o[0:12])),
+                    _tag("sixteen lanes against msrpo::permute", _eq(o[36:40], o[4:8])) if not any(a[:4]) else None)
+    o = op("permute: msrpo::permute, coin Wide, coin Narrow, sixteen lanes", 200, 12, 42, forms)
+    o.add("each edge value", [[e] * 12 for e in E8], lambda a, i: len(set(a)) == 1 and a[0] in E8)
+    o.add("all zero, all p-1", [[0] * 12, [P - 1] * 12])
+    o.gen("edge values crossed", np_, lambda r, i: _edge_state(r), lambda a, i: all(w in E8 for w in a))
+    o.gen("zero capacity, edge rate", np_, lambda r, i: [0] * 4 + _edge_state(r)[4:], lambda a, i: not any(a[:4]) and all(w in E8 for w in a))
+    o.gen("zero capacity, uniform rate", np_, lambda r, i: [0] * 4 + _state(r)[4:], lambda a, i: not any(a[:4]) and all(w < P for w in a))
+    o.gen("capacity 1, 0, 0, 0: a padded row", np_, lambda r, i: [_word(1), 0, 0, 0] + _state(r)[4:], lambda a, i: _vals(a[:4]) == [1, 0, 0, 0])
+    o.gen("non-zero capacity, uniform", np_, lambda r, i: _state(r), lambda a, i: all(a[:4]) and all(w < P for w in a))
+    return ops
+
+
+_BUILDERS = {"gl": _gl, "gld": _gld, "limb": _limb, "acc": _acc, "f252": _f252, "rpo": _rpo}
 
 
 def ops(family, n):

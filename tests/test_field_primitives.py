@@ -17,6 +17,7 @@ import prims  # noqa: E402
 
 CPU_N = 6           # inputs per drawn class in the CPU suite
 GPU_N = {"gl": 2048, "gld": 256, "limb": 256, "acc": 512, "f252": 1024}      # ... on the device: 2^14.5 .. 2^15.6 cases per family
+GPU_N["rpo"] = 64   # the reference of this family costs 1.6 ms per permutation: 170 states in all forms, 2^10 inputs per S-box class
 
 
 def _report(ops_):
