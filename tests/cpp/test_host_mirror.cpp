@@ -133,6 +133,37 @@ int main() {
         REQUIRE(next.to_host() == want);
         auto tree = ms::MerkleTree::from_fri_layer(layer, ff);
         REQUIRE(tree.num_leaves() == ((size_t)1 << log_n) / ff);
+        // apply_drp_rows: the same layer held as two unequal row shards (the first 3/8 of the chunks, then the rest) folds into those words
+        const size_t m = ((size_t)1 << log_n) / ff, cut = 3 * m / 8;
+        std::vector<uint64_t> got;
+        for (size_t first : {(size_t)0, cut}) {
+            const size_t cnt = first ? m - cut : cut;
+            const std::vector<uint64_t> part(ev.begin() + 3 * ff * first, ev.begin() + 3 * ff * (first + cnt));
+            ms::GpuVec<ms::Fq3> shard(pl, part);
+            auto rows = ms::apply_drp_rows(shard, alpha, ff, log_n, first, 1).to_host();
+            REQUIRE(rows.size() == 3 * cnt);
+            got.insert(got.end(), rows.begin(), rows.end());
+        }
+        REQUIRE(got == want);
+    }
+    {   // apply_drp_rows over Fp: a layer of 2^13 evaluations folded by 4 on the coset of 7, whole and as the same two shards
+        const unsigned log_n = 13, ff = 4;
+        auto ev = rnd((size_t)1 << log_n, 79);
+        const std::vector<uint64_t> alpha = rnd(1, 80);
+        std::vector<uint64_t> want((size_t)1 << (log_n - 2));
+        oracle_fri_fold(ev.data(), want.data(), log_n, 1, ff, alpha.data(), 7);
+        REQUIRE(ms::apply_drp(ms::GpuVec<ms::Fp>(pl, ev), alpha, ff, 7).to_host() == want);
+        const size_t m = ((size_t)1 << log_n) / ff, cut = 3 * m / 8;
+        std::vector<uint64_t> got;
+        for (size_t first : {(size_t)0, cut}) {
+            const size_t cnt = first ? m - cut : cut;
+            const std::vector<uint64_t> part(ev.begin() + ff * first, ev.begin() + ff * (first + cnt));
+            ms::GpuVec<ms::Fp> shard(pl, part);
+            auto rows = ms::apply_drp_rows(shard, alpha, ff, log_n, first, 7).to_host();
+            REQUIRE(rows.size() == cnt);
+            got.insert(got.end(), rows.begin(), rows.end());
+        }
+        REQUIRE(got == want);
     }
     {   // constraint evaluation: DAG -> program -> device, against a direct evaluation with the oracle's field ops
         using namespace ms::expr;
