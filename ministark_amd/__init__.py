@@ -8,6 +8,7 @@ from .api import (GOLDILOCKS_FP, GOLDILOCKS_FQ3, STARK252_FP, GL_GENERATOR, GL_P
                   GpuVec, Matrix, MerkleTree, DeviceBytes, Planner, Radix2EvaluationDomain, get_planner, gl_from_mont, gl_to_mont, apply_drp,
                   F252_P, F252_GENERATOR, f252_to_mont_limbs, f252_from_mont_limbs,
                   GpuRpo256ColumnMajor, GpuRpo256RowMajor, gen_rpo_merkle_tree, grind_proof_of_work,
+                  poseidon252_permute, poseidon252_value,
                   scan_affine, running_product, Queries)
 from .extension import (ExtColumn, LogUpColumn, LookupMissing, LookupReport, LookupTuple, build_extension_columns, build_logup_columns,  # noqa: F401
                         lookup_multiplicities, DeviceIndex, SortKey, SortReport, permute_columns, sort_rows,

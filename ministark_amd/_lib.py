@@ -242,10 +242,17 @@ class Lib:
         join_sigs = {
             "ms_join_rows": (i, [vp, i, sz, c_void_pp, u, vp, sz, c_void_pp, u, u, vp, u, c_void_pp, vp]),
         }
+        # include/ministark_hip_poseidon.h: Starknet's Poseidon over the 252-bit field -- the bulk permutation and the commitments
+        poseidon_sigs = {
+            "ms_poseidon252_permute": (i, [vp, sz, vp, vp]),
+            "ms_poseidon252_rows": (i, [vp, sz, c_void_pp, u, vp]),
+            "ms_poseidon252_rows_row_major": (i, [vp, sz, u, vp, vp]),
+            "ms_poseidon252_merkle": (i, [vp, sz, vp, vp]),
+        }
         self.optional = {}
         for name, (res, args) in (list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items())
                                   + list(logup_sigs.items()) + list(rpo_coin_sigs.items()) + list(lookup_sigs.items()) + list(sort_sigs.items()) + list(gap_sigs.items())
-                                  + list(join_sigs.items())):
+                                  + list(join_sigs.items()) + list(poseidon_sigs.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -259,6 +266,7 @@ class Lib:
         self.sort_sigs = sort_sigs
         self.gap_sigs = gap_sigs
         self.join_sigs = join_sigs
+        self.poseidon_sigs = poseidon_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

@@ -286,7 +286,7 @@ def _gather_digests(planner, digests, ndigests, ids):
     return _gather_digests_launch(planner, digests, ndigests, ids)()
 
 
-HASHES = ("sha256", "rpo256", "blake2s", "keccak256", "sha3_256")
+HASHES = ("sha256", "rpo256", "blake2s", "keccak256", "sha3_256", "poseidon252")
 KECCAK_VARIANTS = {"keccak256": 0, "sha3_256": 1}          # MS_KECCAK256 / MS_SHA3_256 of include/ministark_hip_keccak.h
 # the byte hashes share one set of entry points, ms_<prefix>_{rows, rows_row_major, merkle, pow_grind}: name -> (prefix, leading arguments)
 _BYTE_HASHES = {"sha256": ("sha256", ()), "blake2s": ("blake2s", ()),
@@ -373,7 +373,10 @@ class MerkleTree:
       "blake2s" BLAKE2s-256 (blake2::Blake2s256, hashlib.blake2s): the leaves hash the bytes SHA-256 hashes, a merge is one
                 compression instead of two.  Any of the three fields;
       "keccak256" / "sha3_256"  the Keccak sponge with domain byte 0x01 (sha3::Keccak256, the EVM's KECCAK256) / 0x06
-                (hashlib.sha3_256): the same leaf bytes, a merge is one permutation.  Any of the three fields."""
+                (hashlib.sha3_256): the same leaf bytes, a merge is one permutation.  Any of the three fields;
+      "poseidon252"  Starknet's Poseidon (the Hades permutation, t = 3) over STARK252_FP, the algebraic commitment of that field as
+                RPO-256 is Goldilocks': a leaf is hash_many(row), a node hash2(left, right), a digest ONE field element in
+                Montgomery form = 32 bytes (`poseidon252_value` gives its integer).  STARK252_FP matrices and layers only."""
 
     def __init__(self, planner, leaves, nleaves, hash="sha256"):
         if hash not in HASHES:
@@ -385,6 +388,8 @@ class MerkleTree:
         self.nodes = DeviceBytes(planner, nleaves * 32)
         if hash == "rpo256":
             planner.lib.check(planner.lib.ms_rpo256_merkle(planner.handle, nleaves, leaves.ptr, self.nodes.ptr))
+        elif hash == "poseidon252":
+            planner.lib.check(planner.lib.ms_poseidon252_merkle(planner.handle, nleaves, leaves.ptr, self.nodes.ptr))
         else:
             _byte_hash_call(planner, hash, "merkle", nleaves, leaves.ptr, self.nodes.ptr)
 
@@ -404,6 +409,10 @@ class MerkleTree:
                 raise ValueError("RPO-256 absorbs Goldilocks elements")
             words = folding_factor * FIELD_WORDS[evaluations.field]          # a row is N elements = N (or 3 N) Fp words in memory order
             pl.lib.check(pl.lib.ms_rpo256_rows_row_major(pl.handle, nrows, words, evaluations.ptr, leaves.ptr))
+        elif hash == "poseidon252":
+            if evaluations.field != STARK252_FP:
+                raise ValueError("Poseidon absorbs elements of the 252-bit field (STARK252_FP)")
+            pl.lib.check(pl.lib.ms_poseidon252_rows_row_major(pl.handle, nrows, folding_factor, evaluations.ptr, leaves.ptr))
         elif hash in _BYTE_HASHES:
             _byte_hash_call(pl, hash, "rows_row_major", evaluations.field, nrows, folding_factor, evaluations.ptr, leaves.ptr)
         else:
@@ -763,12 +772,16 @@ class Matrix:
     def hash_rows(self, hash="sha256"):
         """`hash_rows::<F, H>` (src/merkle.rs:412-436, src/matrix.rs:254-280): one digest per row ->
         DeviceBytes of num_rows x 32.  H = Sha256HashFn ("sha256"), RPO-256 ("rpo256", Goldilocks columns), BLAKE2s-256 ("blake2s"),
-        Keccak-256 ("keccak256") or SHA3-256 ("sha3_256")."""
+        Keccak-256 ("keccak256"), SHA3-256 ("sha3_256") or Starknet's Poseidon ("poseidon252", STARK252_FP columns: a digest is one element)."""
         pl = self.planner
         n = self.num_rows()
+        if hash == "poseidon252" and self.field != STARK252_FP:
+            raise ValueError("Poseidon absorbs elements of the 252-bit field (STARK252_FP)")
         leaves = DeviceBytes(pl, n * 32)
         if hash == "rpo256":
             pl.lib.check(pl.lib.ms_rpo256_rows_field(pl.handle, self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr))
+        elif hash == "poseidon252":
+            pl.lib.check(pl.lib.ms_poseidon252_rows(pl.handle, n, _ptr_array(self.columns), len(self.columns), leaves.ptr))
         elif hash in _BYTE_HASHES:
             _byte_hash_call(pl, hash, "rows", self.field, n, _ptr_array(self.columns), len(self.columns), leaves.ptr)
         else:
@@ -923,9 +936,28 @@ def gen_rpo_merkle_tree(leaves):
     return nodes
 
 
+def poseidon252_permute(planner, states):
+    """The bulk Hades permutation (ms_poseidon252_permute): `states` is a GpuVec of STARK252_FP holding n states of three elements,
+    row-major [n][3] -> a new GpuVec of the same shape.  What a Poseidon-builtin trace generator calls."""
+    if states.field != STARK252_FP or len(states) % 3:
+        raise ValueError("poseidon252_permute: a STARK252_FP vector of 3 n elements")
+    out = GpuVec(planner, len(states), STARK252_FP)
+    planner.lib.check(planner.lib.ms_poseidon252_permute(planner.handle, len(states) // 3, states.ptr, out.ptr))
+    return out
+
+
+def poseidon252_value(digest_bytes):
+    """The canonical integer of a "poseidon252" digest (a leaf, a node, a root): the 32 bytes are one field element, four
+    little-endian u64 in Montgomery form."""
+    digest_bytes = bytes(digest_bytes)
+    if len(digest_bytes) != 32:
+        raise ValueError("a digest is 32 bytes")
+    return (int.from_bytes(digest_bytes, "little") * pow(1 << 256, -1, F252_P)) % F252_P
+
+
 def pow_hash(commitment_hash):
     """The proof-of-work hash of a prover that commits with `commitment_hash`: BLAKE2s grinds with BLAKE2s, Keccak-256 and SHA3-256
-    with themselves; SHA-256 and RPO-256 provers grind with SHA-256, as they always have."""
+    with themselves; SHA-256, RPO-256 and Poseidon provers grind with SHA-256, as they always have."""
     return commitment_hash if commitment_hash in ("blake2s", "keccak256", "sha3_256") else "sha256"
 
 

@@ -24,6 +24,7 @@
 
 #include "../../../include/ministark_hip.h"
 #include "../../../include/ministark_hip_keccak.h"
+#include "../../../include/ministark_hip_poseidon.h"
 
 namespace ms {
 
@@ -317,8 +318,13 @@ public:
 // H of MatrixMerkleTreeImpl<H> (src/merkle.rs:296-361): Sha256HashFn (src/hash.rs:58-100), RPO-256 over
 // Goldilocks (gpu/src/plan.rs:32-174, README.md:90) or BLAKE2s-256 (any field; the bytes SHA-256 hashes, one compression per
 // merge), or the Keccak sponge as Keccak-256 (the EVM's KECCAK256) / SHA3-256 (any field; the same bytes, one permutation per merge).
+// Poseidon252 is Starknet's Poseidon over the 252-bit field (include/ministark_hip_poseidon.h), the algebraic commitment of Fp252 as RPO-256
+// is Goldilocks': a digest is one field element in Montgomery form; matrices and layers of Fp252 only (std::invalid_argument otherwise).
 // All digests are 32 bytes, proofs have the same shape.
-enum class Hash { Sha256, Rpo256, Blake2s, Keccak256, Sha3_256 };
+enum class Hash { Sha256, Rpo256, Blake2s, Keccak256, Sha3_256, Poseidon252 };
+inline void poseidon_field(int field) {
+    if (field != MS_STARK252_FP) throw std::invalid_argument("Hash::Poseidon252 absorbs elements of the 252-bit field (ms::Fp252)");
+}
 inline int keccak_variant(Hash h) { return h == Hash::Sha3_256 ? MS_SHA3_256 : MS_KECCAK256; }        // `variant` of ms_keccak_*
 // One dispatch per operation: the entry point of `h` (the RPO-256 ones differ in shape: digests of field elements, rows counted in Fp words).
 inline int hash_rows(ms_ctx* ctx, Hash h, int field, size_t nrows, const void* const* d_cols, unsigned ncols, void* d_leaves) {
@@ -326,6 +332,7 @@ inline int hash_rows(ms_ctx* ctx, Hash h, int field, size_t nrows, const void* c
         case Hash::Sha256: return ms_sha256_rows(ctx, field, nrows, d_cols, ncols, d_leaves);
         case Hash::Blake2s: return ms_blake2s_rows(ctx, field, nrows, d_cols, ncols, d_leaves);
         case Hash::Keccak256: case Hash::Sha3_256: return ms_keccak_rows(ctx, keccak_variant(h), field, nrows, d_cols, ncols, d_leaves);
+        case Hash::Poseidon252: poseidon_field(field); return ms_poseidon252_rows(ctx, nrows, d_cols, ncols, d_leaves);
         case Hash::Rpo256: break;
     }
     return ms_rpo256_rows_field(ctx, field, nrows, d_cols, ncols, d_leaves);
@@ -335,6 +342,7 @@ inline int hash_rows_row_major(ms_ctx* ctx, Hash h, int field, size_t nrows, uns
         case Hash::Sha256: return ms_sha256_rows_row_major(ctx, field, nrows, ncols, d_matrix, d_leaves);
         case Hash::Blake2s: return ms_blake2s_rows_row_major(ctx, field, nrows, ncols, d_matrix, d_leaves);
         case Hash::Keccak256: case Hash::Sha3_256: return ms_keccak_rows_row_major(ctx, keccak_variant(h), field, nrows, ncols, d_matrix, d_leaves);
+        case Hash::Poseidon252: poseidon_field(field); return ms_poseidon252_rows_row_major(ctx, nrows, ncols, d_matrix, d_leaves);
         case Hash::Rpo256: break;
     }
     return ms_rpo256_rows_row_major(ctx, nrows, ncols * (unsigned)(ms_field_bytes(field) / 8), d_matrix, d_leaves);
@@ -344,16 +352,17 @@ inline int hash_merkle(ms_ctx* ctx, Hash h, size_t nleaves, const void* d_leaves
         case Hash::Sha256: return ms_sha256_merkle(ctx, nleaves, d_leaves, d_nodes);
         case Hash::Blake2s: return ms_blake2s_merkle(ctx, nleaves, d_leaves, d_nodes);
         case Hash::Keccak256: case Hash::Sha3_256: return ms_keccak_merkle(ctx, keccak_variant(h), nleaves, d_leaves, d_nodes);
+        case Hash::Poseidon252: return ms_poseidon252_merkle(ctx, nleaves, d_leaves, d_nodes);
         case Hash::Rpo256: break;
     }
     return ms_rpo256_merkle(ctx, nleaves, d_leaves, d_nodes);
 }
-// an RPO-256 prover grinds with SHA-256
+// an RPO-256 prover grinds with SHA-256, and so does a Poseidon one
 inline int hash_pow_grind(ms_ctx* ctx, Hash h, const void* h_seed32, unsigned bits, uint64_t max_nonce, uint64_t* nonce) {
     switch (h) {
         case Hash::Blake2s: return ms_blake2s_pow_grind(ctx, h_seed32, bits, max_nonce, nonce);
         case Hash::Keccak256: case Hash::Sha3_256: return ms_keccak_pow_grind(ctx, keccak_variant(h), h_seed32, bits, max_nonce, nonce);
-        case Hash::Sha256: case Hash::Rpo256: break;
+        case Hash::Sha256: case Hash::Rpo256: case Hash::Poseidon252: break;
     }
     return ms_sha256_pow_grind(ctx, h_seed32, bits, max_nonce, nonce);
 }
@@ -440,5 +449,14 @@ private:
     }
     Planner* pl_; size_t n_; void* leaves_ = nullptr; void* nodes_ = nullptr;
 };
+
+// The bulk Hades permutation (ms_poseidon252_permute): `states` holds n states of three elements, row-major [n][3] -> the permuted
+// states in a new vector.  What a Poseidon-builtin trace generator calls.
+inline GpuVec<Fp252> poseidon252_permute(const GpuVec<Fp252>& states) {
+    if (states.len() % 3) throw std::invalid_argument("poseidon252_permute: a vector of 3 n elements");
+    GpuVec<Fp252> out(states.planner(), states.len());
+    check(ms_poseidon252_permute(states.planner().ctx(), states.len() / 3, states.ptr(), out.ptr()));
+    return out;
+}
 
 }  // namespace ms

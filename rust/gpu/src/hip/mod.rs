@@ -26,11 +26,12 @@ pub mod sys_gaps;
 pub mod sys_join;
 pub mod sys_logup;
 pub mod sys_lookup;
+pub mod sys_poseidon;
 pub mod sys_rpo_coin;
 pub mod sys_sort;
 pub mod sys_transcript;
 pub mod utils;
 
-pub use plan::{evaluate_device, gen_rpo_merkle_tree, get_planner, lde_device, keccak_commit_device, sha256_commit_device, GpuFft, GpuIfft, GpuRpo256ColumnMajor,
+pub use plan::{evaluate_device, gen_rpo_merkle_tree, get_planner, lde_device, keccak_commit_device, poseidon252_commit_device, sha256_commit_device, GpuFft, GpuIfft, GpuRpo256ColumnMajor,
                GpuRpo256RowMajor, Planner};
 pub use utils::{bit_reverse_device, field_id, DeviceVec};

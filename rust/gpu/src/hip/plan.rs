@@ -3,6 +3,7 @@
 //! `*_device` methods are the resident variants the patched callers use (rust/patches/).
 use super::sys;
 use super::sys_keccak;
+use super::sys_poseidon;
 use super::utils::{field_id, DeviceVec};
 use crate::GpuField;
 use ark_poly::domain::Radix2EvaluationDomain;
@@ -157,6 +158,20 @@ pub fn keccak_commit_device<F: GpuField>(variant: c_int, columns: &[DeviceVec<F>
     let cols: Vec<*const c_void> = columns.iter().map(|c| c.device_ptr() as *const c_void).collect();
     sys::check(unsafe { sys_keccak::ms_keccak_rows(get_planner().ctx(), variant, field_id::<F>(), n, cols.as_ptr(), cols.len() as u32, leaves.device_ptr()) });
     sys::check(unsafe { sys_keccak::ms_keccak_merkle(get_planner().ctx(), variant, n, leaves.device_ptr() as *const c_void, nodes.device_ptr()) });
+    (leaves, nodes)
+}
+
+/// `sha256_commit_device` with Starknet's Poseidon (Hades, t = 3) over the 252-bit field: a leaf is `hash_many(row)`, a node
+/// `hash2(left, right)`, and a digest is ONE field element in Montgomery form -- the 32 bytes of an `Fp` as arkworks holds it, so
+/// the tree has the layout of the byte hashes' trees.  Columns of the 252-bit field only.  -> (leaves, nodes); nodes[1] is the root.
+pub fn poseidon252_commit_device<F: GpuField>(columns: &[DeviceVec<F>]) -> (DeviceVec<[u8; 32]>, DeviceVec<[u8; 32]>) {
+    assert_eq!(field_id::<F>(), sys::MS_STARK252_FP, "Poseidon absorbs elements of the 252-bit field");
+    let n = columns[0].len();
+    let leaves = DeviceVec::<[u8; 32]>::with_len(n);
+    let nodes = DeviceVec::<[u8; 32]>::with_len(n);
+    let cols: Vec<*const c_void> = columns.iter().map(|c| c.device_ptr() as *const c_void).collect();
+    sys::check(unsafe { sys_poseidon::ms_poseidon252_rows(get_planner().ctx(), n, cols.as_ptr(), cols.len() as u32, leaves.device_ptr()) });
+    sys::check(unsafe { sys_poseidon::ms_poseidon252_merkle(get_planner().ctx(), n, leaves.device_ptr() as *const c_void, nodes.device_ptr()) });
     (leaves, nodes)
 }
 

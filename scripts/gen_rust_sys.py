@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generate rust/gpu/src/hip/sys.rs -- the raw `extern "C"` bindings of the reference-side shim -- from
-include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h, sys_gaps.rs from include/ministark_hip_gaps.h and sys_join.rs from include/ministark_hip_join.h.  tests/test_rust_shim.py re-runs the parser and
+include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h, sys_gaps.rs from include/ministark_hip_gaps.h, sys_join.rs from include/ministark_hip_join.h and sys_poseidon.rs from include/ministark_hip_poseidon.h.  tests/test_rust_shim.py re-runs the parser and
 checks the committed file against the header, which stands in for compiling it (no Rust toolchain in the image).
 
     python scripts/gen_rust_sys.py            # rewrite rust/gpu/src/hip/sys.rs
@@ -30,6 +30,8 @@ GAPS_HEADER = os.path.join(ROOT, "include", "ministark_hip_gaps.h")
 GAPS_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_gaps.rs")
 JOIN_HEADER = os.path.join(ROOT, "include", "ministark_hip_join.h")
 JOIN_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_join.rs")
+POSEIDON_HEADER = os.path.join(ROOT, "include", "ministark_hip_poseidon.h")
+POSEIDON_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_poseidon.rs")
 
 BASE = {"int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "long": "c_long", "size_t": "usize", "uint64_t": "u64",
         "uint32_t": "u32", "char": "c_char", "unsigned char": "u8", "void": "c_void", "ms_ctx": "ms_ctx", "ms_ntt_plan": "ms_ntt_plan", "ms_xchg_op": "ms_xchg_op", "ms_p2p_op": "ms_p2p_op", "ms_jit_stats": "ms_jit_stats"}
@@ -367,6 +369,28 @@ def join_prototypes():
     return prototypes(text[text.index("#define MINISTARK_HIP_JOIN_H"):])
 
 
+def render_poseidon(protos):
+    """sys_poseidon.rs: the entry points of include/ministark_hip_poseidon.h (Starknet's Poseidon over the 252-bit field: the bulk
+    permutation and the commitments), on sys.rs's types"""
+    lines = ["// GENERATED by scripts/gen_rust_sys.py from include/ministark_hip_poseidon.h -- do not edit by hand.",
+             "// Raw bindings of the Poseidon layer of libministark_hip.so (INTEGRATION.md section 3g).",
+             "#![allow(non_camel_case_types)]",
+             "use core::ffi::{c_int, c_uint, c_void};",
+             "use super::sys::ms_ctx;",
+             "",
+             '#[link(name = "ministark_hip")]', 'extern "C" {']
+    for name, ret, plist in protos:
+        args = ", ".join(f"{(p + '_') if p in RUST_KEYWORDS else p}: {t}" for p, t in plist)
+        lines.append(f"    pub fn {name}({args})" + (f" -> {ret};" if ret else ";"))
+    lines += ["}", ""]
+    return "\n".join(lines)
+
+
+def poseidon_prototypes():
+    text = open(POSEIDON_HEADER).read()
+    return prototypes(text[text.index("#define MINISTARK_HIP_POSEIDON_H"):])
+
+
 def main():
     protos = prototypes(open(HEADER).read())
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
@@ -409,6 +433,10 @@ def main():
     with open(JOIN_OUT, "w") as f:
         f.write(render_join(protos))
     print(f"{len(protos)} prototypes -> {JOIN_OUT}")
+    protos = poseidon_prototypes()
+    with open(POSEIDON_OUT, "w") as f:
+        f.write(render_poseidon(protos))
+    print(f"{len(protos)} prototypes -> {POSEIDON_OUT}")
 
 
 if __name__ == "__main__":
