@@ -48,6 +48,11 @@ class CoinState(ctypes.Structure):
                 ("bytes", ctypes.c_uint8 * 32)]
 
 
+class HadesCoinState(ctypes.Structure):
+    """`ms_hades_coin_state` of include/ministark_hip_hades_coin.h: the Poseidon coin's digest (Montgomery words) and its draw counter."""
+    _fields_ = [("digest", ctypes.c_uint64 * 4), ("n_draws", ctypes.c_uint64), ("pad", ctypes.c_uint32 * 4)]
+
+
 class RpoCoinState(ctypes.Structure):
     """`ms_rpo_coin_state` of include/ministark_hip_rpo_coin.h: the RPO-256 coin's sponge (Montgomery words) and its read position."""
     _fields_ = [("s", ctypes.c_uint64 * 12), ("pos", ctypes.c_uint32), ("pad", ctypes.c_uint32 * 7)]
@@ -249,10 +254,24 @@ class Lib:
             "ms_poseidon252_rows_row_major": (i, [vp, sz, u, vp, vp]),
             "ms_poseidon252_merkle": (i, [vp, sz, vp, vp]),
         }
+        # include/ministark_hip_hades_coin.h: the Poseidon public coin of the 252-bit field (each the twin of its ms_rpo_coin_* namesake)
+        hades_coin_sigs = {
+            "ms_hades_coin_create": (i, [vp, vp, c_void_pp]),
+            "ms_hades_coin_destroy": (i, [vp, vp]),
+            "ms_hades_coin_read": (i, [vp, vp, vp]),
+            "ms_hades_coin_write": (i, [vp, vp, vp]),
+            "ms_hades_coin_reseed_digest": (i, [vp, vp, vp]),
+            "ms_hades_coin_reseed_int": (i, [vp, vp, ctypes.c_uint64]),
+            "ms_hades_coin_reseed_elements": (i, [vp, vp, i, vp, sz]),
+            "ms_hades_coin_reseed_elements_host": (i, [vp, vp, i, vp, sz]),
+            "ms_hades_coin_draw": (i, [vp, vp, i, sz, vp]),
+            "ms_hades_coin_draw_queries": (i, [vp, vp, sz, sz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(sz)]),
+            "ms_hades_coin_pow_grind": (i, [vp, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        }
         self.optional = {}
         for name, (res, args) in (list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items())
                                   + list(logup_sigs.items()) + list(rpo_coin_sigs.items()) + list(lookup_sigs.items()) + list(sort_sigs.items()) + list(gap_sigs.items())
-                                  + list(join_sigs.items()) + list(poseidon_sigs.items())):
+                                  + list(join_sigs.items()) + list(poseidon_sigs.items()) + list(hades_coin_sigs.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -267,6 +286,7 @@ class Lib:
         self.gap_sigs = gap_sigs
         self.join_sigs = join_sigs
         self.poseidon_sigs = poseidon_sigs
+        self.hades_coin_sigs = hades_coin_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

@@ -2,13 +2,15 @@
 in device memory: the ms_coin_* entry points of include/ministark_hip_transcript.h.  A commitment's root is absorbed where the tree builder left it
 (`MerkleTree.root_ptr()`), a drawn challenge stays on the device (`draw` returns a GpuVec that `api.apply_drp` hands to
 ms_fri_fold_dev), and none of the reseeds or draws waits for the device.  `RpoCoin` is the algebraic coin of
-include/ministark_hip_rpo_coin.h (ms_rpo_coin_*): the same methods over an RPO-256 sponge that absorbs and draws field elements."""
+include/ministark_hip_rpo_coin.h (ms_rpo_coin_*): the same methods over an RPO-256 sponge that absorbs and draws field elements.
+`PoseidonCoin` is the algebraic coin of the 252-bit field (include/ministark_hip_hades_coin.h, ms_hades_coin_*): the same methods over
+one field element and a draw counter."""
 import ctypes
 
 import numpy as np
 
 from . import _lib
-from .api import FIELD_WORDS, GL_P, DeviceBytes, GpuVec, gl_from_mont, gl_to_mont
+from .api import F252_P, FIELD_WORDS, GL_P, DeviceBytes, GpuVec, f252_from_mont_limbs, f252_to_mont_limbs, gl_from_mont, gl_to_mont
 
 HASH_IDS = {"sha256": 0, "blake2s": 1, "keccak256": 3, "sha3_256": 4}        # 2 stays unknown: the RPO-256 coin is RpoCoin, a family of its own
 
@@ -185,6 +187,104 @@ class RpoCoin:
     def close(self):
         if self.ptr and self.planner.handle:
             self.planner.lib.ms_rpo_coin_destroy(self.planner.handle, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def poseidon_seed(seed):
+    """The seed of a `PoseidonCoin`: one element of the 252-bit field, as an integer below p or as 32 bytes read little-endian."""
+    if isinstance(seed, (bytes, bytearray, memoryview)):
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("the coin's seed is 32 bytes (one little-endian integer) or an integer")
+        value = int.from_bytes(seed, "little")
+    else:
+        value = int(seed)
+    if not 0 <= value < F252_P:
+        raise ValueError("the seed of a Poseidon coin is an element of the 252-bit field: below p")
+    return value
+
+
+class PoseidonCoin:
+    """The Poseidon public coin of the 252-bit field (ms_hades_coin_*): one field element and a draw counter on the device.  It has
+    `RpoCoin`'s methods, so `pipeline.prove` holds either.  seed: see `poseidon_seed`.  The rules are in
+    include/ministark_hip_hades_coin.h: digest = hash2(digest, x) absorbs, permute(digest, n_draws + i, 3)[0] draws, tag 4 grinds."""
+
+    hash = "poseidon252"
+
+    def __init__(self, planner, seed):
+        self.planner, self.ptr = planner, None
+        value = poseidon_seed(seed)
+        h = ctypes.c_void_p()
+        buf = (ctypes.c_uint64 * 4)(*[(value >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)])      # canonical words: the library converts
+        planner.lib.check(planner.lib.ms_hades_coin_create(planner.handle, buf, ctypes.byref(h)))
+        self.ptr = h.value
+
+    def _call(self, fn, *args):
+        self.planner.lib.check(fn(self.planner.handle, self.ptr, *args))
+
+    def reseed_digest(self, digest):
+        """Absorb one element of device memory: a DeviceBytes (its first 32 bytes) or a device address, e.g. `tree.root_ptr()` of a
+        "poseidon252" tree.  Asynchronous."""
+        self._call(self.planner.lib.ms_hades_coin_reseed_digest, digest.ptr if isinstance(digest, DeviceBytes) else int(digest))
+
+    def reseed_int(self, value):
+        """Absorb a u64 (the proof-of-work nonce).  Asynchronous."""
+        self._call(self.planner.lib.ms_hades_coin_reseed_int, int(value))
+
+    def reseed_elements(self, elems, field=None):
+        """Absorb hash_many of field elements: a GpuVec, or numpy u64 Montgomery words of STARK252_FP elements on the host.  Asynchronous."""
+        L = self.planner.lib
+        if isinstance(elems, GpuVec):
+            self._call(L.ms_hades_coin_reseed_elements, elems.field, elems.ptr, len(elems))
+            return
+        if field is None:
+            raise ValueError("reseed_elements: host elements need their field")
+        arr = np.ascontiguousarray(elems, dtype=np.uint64).ravel()
+        assert arr.size % FIELD_WORDS[field] == 0
+        self._call(L.ms_hades_coin_reseed_elements_host, field, arr.ctypes.data, arr.size // FIELD_WORDS[field])
+
+    def draw(self, field, count=1):
+        """-> GpuVec of `count` elements of STARK252_FP (Montgomery form), left on the device.  Asynchronous."""
+        out = GpuVec(self.planner, count, field)
+        self._call(self.planner.lib.ms_hades_coin_draw, field, count, out.ptr)
+        return out
+
+    def draw_queries(self, max_n, domain_size):
+        """The distinct positions in ascending order; domain_size is a power of two up to 2^32.  Blocks."""
+        pos = np.empty(max(max_n, 1), dtype=np.uint64)
+        n = ctypes.c_size_t(0)
+        self._call(self.planner.lib.ms_hades_coin_draw_queries, max_n, domain_size, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(n))
+        return [int(p) for p in pos[: n.value]]
+
+    def grind(self, bits, max_nonce=1 << 40):
+        """The smallest nonce n >= 1 such that permute(digest, n, 4)[0] has its low `bits` bits zero; the coin is not reseeded.  Blocks."""
+        out = ctypes.c_uint64(0)
+        self._call(self.planner.lib.ms_hades_coin_pow_grind, bits, max_nonce, ctypes.byref(out))
+        return out.value
+
+    def state(self):
+        """-> {"digest": the digest as a canonical integer, "n_draws": the draws made since the last reseed}.  Blocks."""
+        st = _lib.HadesCoinState()
+        self._call(self.planner.lib.ms_hades_coin_read, ctypes.byref(st))
+        return {"digest": f252_from_mont_limbs(st.digest), "n_draws": int(st.n_draws)}
+
+    def set_state(self, digest, n_draws):
+        """ms_hades_coin_write: replace the state (tests, checkpoints); digest: a canonical integer below p."""
+        st = _lib.HadesCoinState()
+        for k, v in enumerate(f252_to_mont_limbs(int(digest) % F252_P)):
+            st.digest[k] = int(v)
+        st.n_draws = n_draws
+        self._call(self.planner.lib.ms_hades_coin_write, ctypes.byref(st))
+
+    def close(self):
+        if self.ptr and self.planner.handle:
+            self.planner.lib.ms_hades_coin_destroy(self.planner.handle, self.ptr)
         self.ptr = None
 
     def __del__(self):

@@ -11,6 +11,7 @@
 //   grind_proof_of_work               src/random.rs:48-55
 //   PublicCoin                        src/random.rs:61-141, as ProverChannel uses it (src/channel.rs:46-100); state on the device
 //   RpoCoin                           the same calls on the algebraic RPO-256 coin (ministark_hip_rpo_coin.h)
+//   PoseidonCoin                      the same calls on the algebraic coin of the 252-bit field (ministark_hip_hades_coin.h)
 //   GpuRpo256ColumnMajor / RowMajor / gen_rpo_merkle_tree   gpu/src/plan.rs:32-174
 // Host values of Fq are canonical integers: FqVal{c0,c1,c2} (c1 = c2 = 0 when Fq = Fp).
 #pragma once
@@ -19,6 +20,7 @@
 #include "../../../include/ministark_hip_ext.h"
 #include "../../../include/ministark_hip_logup.h"
 #include "../../../include/ministark_hip_rpo_coin.h"
+#include "../../../include/ministark_hip_hades_coin.h"
 #include "../../../include/ministark_hip_lookup.h"
 #include "../../../include/ministark_hip_sort.h"
 #include "../../../include/ministark_hip_gaps.h"
@@ -493,6 +495,41 @@ public:
     }
     uint64_t grind(unsigned bits, uint64_t max_nonce = (uint64_t)1 << 40) { uint64_t nonce = 0; check(ms_rpo_coin_pow_grind(pl_->ctx(), coin_, bits, max_nonce, &nonce)); return nonce; }
     ms_rpo_coin_state state() const { ms_rpo_coin_state st; check(ms_rpo_coin_read(pl_->ctx(), coin_, &st)); return st; }
+private:
+    Planner* pl_;
+    void* coin_ = nullptr;
+};
+
+// The Poseidon public coin of the 252-bit field (ms_hades_coin_*, include/ministark_hip_hades_coin.h): RpoCoin's methods over one field
+// element and a draw counter, for an Fp252 prover that commits with Hash::Poseidon252 and whose verifier runs inside another proof.
+// seed: one element below p as four canonical little-endian words.  The reseeds and draw() enqueue and return; draw_queries, grind and
+// state wait for the device.  state(): the digest in Montgomery words, as stored.
+class PoseidonCoin {
+public:
+    PoseidonCoin(Planner& pl, const std::array<uint64_t, 4>& seed) : pl_(&pl) {
+        lib252::f252::E e;
+        for (int q = 0; q < 4; q++) e.l[q] = seed[q];
+        if (lib252::f252::geq_p(e)) throw std::invalid_argument("PoseidonCoin: the seed is below p");
+        check(ms_hades_coin_create(pl.ctx(), seed.data(), &coin_));
+    }
+    ~PoseidonCoin() { if (coin_) ms_hades_coin_destroy(pl_->ctx(), coin_); }
+    PoseidonCoin(const PoseidonCoin&) = delete; PoseidonCoin& operator=(const PoseidonCoin&) = delete;
+    void reseed_digest(const void* d_digest) { check(ms_hades_coin_reseed_digest(pl_->ctx(), coin_, d_digest)); }   // e.g. the root_ptr() of a Poseidon252 tree
+    void reseed_int(uint64_t value) { check(ms_hades_coin_reseed_int(pl_->ctx(), coin_, value)); }
+    template <class F> void reseed_elements(const GpuVec<F>& elems, size_t count) { check(ms_hades_coin_reseed_elements(pl_->ctx(), coin_, F::id, elems.ptr(), count)); }
+    template <class F> void reseed_elements(const GpuVec<F>& elems) { reseed_elements(elems, elems.len()); }
+    template <class F> void reseed_elements(const std::vector<uint64_t>& mont_words) {                            // host elements, Montgomery words
+        check(ms_hades_coin_reseed_elements_host(pl_->ctx(), coin_, F::id, mont_words.data(), mont_words.size() / F::words));
+    }
+    template <class F> GpuVec<F> draw(size_t count = 1) { GpuVec<F> out(*pl_, count); check(ms_hades_coin_draw(pl_->ctx(), coin_, F::id, count, out.ptr())); return out; }
+    std::vector<size_t> draw_queries(size_t max_n, size_t domain_size) {
+        std::vector<uint64_t> pos(max_n ? max_n : 1);
+        size_t n = 0;
+        check(ms_hades_coin_draw_queries(pl_->ctx(), coin_, max_n, domain_size, pos.data(), &n));
+        return std::vector<size_t>(pos.begin(), pos.begin() + n);
+    }
+    uint64_t grind(unsigned bits, uint64_t max_nonce = (uint64_t)1 << 40) { uint64_t nonce = 0; check(ms_hades_coin_pow_grind(pl_->ctx(), coin_, bits, max_nonce, &nonce)); return nonce; }
+    ms_hades_coin_state state() const { ms_hades_coin_state st; check(ms_hades_coin_read(pl_->ctx(), coin_, &st)); return st; }
 private:
     Planner* pl_;
     void* coin_ = nullptr;

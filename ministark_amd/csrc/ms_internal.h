@@ -71,6 +71,8 @@ struct ms_ctx {
     std::map<void*, size_t> live;            // size of every block handed out by ms_alloc
     std::map<void*, int> coins;              // public coins created on this context (ms_coin.cpp): device state -> MS_HASH_*
     std::map<void*, int> rpo_coins;          // RPO-256 coins (ms_rpo_coin.cpp): a registry of its own, so that neither family takes the other's handles
+    std::map<void*, uint64_t> hades_coins;   // Poseidon coins of the 252-bit field (ms_hades_coin.cpp), again a registry of its own; the value mirrors the
+                                             // record's n_draws (every change of it is a call of this library), so a draw past 2^64 is refused without a host wait
     // pinned staging ring for the small host arrays entry points take (query positions, digest indices): the copy to the
     // device is then truly asynchronous and the call does not drain the stream (stage_upload)
     char* stage = nullptr;

@@ -665,13 +665,15 @@ def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, foldi
     host itself needs (challenges and composition coefficients for the evaluator, z, DEEP coefficients) are downloaded where they are needed,
     as the reference's are.  hints: canonical integers; H of the coin: BLAKE2s for a BLAKE2s prover, else SHA-256.
     coin: None keeps that choice (`pow_hash(hash)`); "rpo256" runs the whole transcript, proof-of-work included, on the algebraic
-    `coin.RpoCoin` -- it needs hash="rpo256" and a Goldilocks `field` (fq Fp or Fq3), and takes seed32 as `coin.rpo_seed` does.
+    `coin.RpoCoin` -- it needs hash="rpo256" and a Goldilocks `field` (fq Fp or Fq3), and takes seed32 as `coin.rpo_seed` does;
+    "poseidon252" does the same on `coin.PoseidonCoin` -- it needs hash="poseidon252" and field=STARK252_FP, and takes seed32 as
+    `coin.poseidon_seed` does.
     Returns what prove_phases returns (without timings), plus the draws as canonical values (3-tuples when fq is Fq3): air_challenges,
     challenges (the composition coefficients), z, deep, fri_alphas, positions; `extension_root` when there is an extension trace.  keep=True
     adds the intermediate device objects of prove_phases, `ext_trace` / `ext_polys` / `ext_lde`, the coin, and `remainder_poly`: all n_rem
     coefficients of the remainder's interpolant, of which `remainder_coeffs` are the first n_rem / blowup (fri.rs:244 asserts the rest vanish)."""
     from .api import FIELD_WORDS, GOLDILOCKS_FQ3, GatherBatch, GpuVec
-    from .coin import PublicCoin, RpoCoin
+    from .coin import PoseidonCoin, PublicCoin, RpoCoin
     from .extension import build_extension_columns
     pl = planner
     if field not in (GOLDILOCKS_FP, STARK252_FP):
@@ -686,10 +688,12 @@ def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, foldi
         raise ValueError("prove: poseidon252 absorbs elements of the 252-bit field: it needs field=STARK252_FP (Goldilocks commits algebraically with rpo256)")
     if trace.field != field:
         raise ValueError("prove: the trace is not over `field`")
-    if coin not in (None, "rpo256"):
-        raise ValueError('prove: coin is None (the byte coin of `hash`) or "rpo256"')
+    if coin not in (None, "rpo256", "poseidon252"):
+        raise ValueError('prove: coin is None (the byte coin of `hash`), "rpo256" or "poseidon252"')
     if coin == "rpo256" and (hash != "rpo256" or field != GOLDILOCKS_FP):
         raise ValueError('prove: coin="rpo256" absorbs RPO-256 roots and Goldilocks elements: it needs hash="rpo256" and field=GOLDILOCKS_FP')
+    if coin == "poseidon252" and (hash != "poseidon252" or field != STARK252_FP):
+        raise ValueError('prove: coin="poseidon252" absorbs Poseidon roots and elements of the 252-bit field: it needs hash="poseidon252" and field=STARK252_FP')
     h = field_generator(field)
     n_t = trace.num_rows()
     n_lde = n_t * blowup
@@ -698,7 +702,7 @@ def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, foldi
     n_ce = n_t * ce_blowup
     trace_dom, lde_dom, ce_dom = Radix2EvaluationDomain(n_t, 1, field), Radix2EvaluationDomain(n_lde, h, field), Radix2EvaluationDomain(n_ce, h, field)
     V = FIELD_WORDS[fq]
-    coin = RpoCoin(pl, seed32) if coin == "rpo256" else PublicCoin(pl, seed32, pow_hash(hash))
+    coin = RpoCoin(pl, seed32) if coin == "rpo256" else PoseidonCoin(pl, seed32) if coin == "poseidon252" else PublicCoin(pl, seed32, pow_hash(hash))
     out = {}
 
     base_polys = trace.interpolate(trace_dom)                                  # prover.rs:50

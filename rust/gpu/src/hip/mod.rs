@@ -23,6 +23,7 @@ pub mod sys;
 pub mod sys_keccak;
 pub mod sys_ext;
 pub mod sys_gaps;
+pub mod sys_hades_coin;
 pub mod sys_join;
 pub mod sys_logup;
 pub mod sys_lookup;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generate rust/gpu/src/hip/sys.rs -- the raw `extern "C"` bindings of the reference-side shim -- from
-include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h, sys_gaps.rs from include/ministark_hip_gaps.h, sys_join.rs from include/ministark_hip_join.h and sys_poseidon.rs from include/ministark_hip_poseidon.h.  tests/test_rust_shim.py re-runs the parser and
+include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h, sys_gaps.rs from include/ministark_hip_gaps.h, sys_join.rs from include/ministark_hip_join.h, sys_poseidon.rs from include/ministark_hip_poseidon.h and sys_hades_coin.rs from include/ministark_hip_hades_coin.h.  tests/test_rust_shim.py re-runs the parser and
 checks the committed file against the header, which stands in for compiling it (no Rust toolchain in the image).
 
     python scripts/gen_rust_sys.py            # rewrite rust/gpu/src/hip/sys.rs
@@ -32,6 +32,8 @@ JOIN_HEADER = os.path.join(ROOT, "include", "ministark_hip_join.h")
 JOIN_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_join.rs")
 POSEIDON_HEADER = os.path.join(ROOT, "include", "ministark_hip_poseidon.h")
 POSEIDON_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_poseidon.rs")
+HADES_COIN_HEADER = os.path.join(ROOT, "include", "ministark_hip_hades_coin.h")
+HADES_COIN_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_hades_coin.rs")
 
 BASE = {"int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "long": "c_long", "size_t": "usize", "uint64_t": "u64",
         "uint32_t": "u32", "char": "c_char", "unsigned char": "u8", "void": "c_void", "ms_ctx": "ms_ctx", "ms_ntt_plan": "ms_ntt_plan", "ms_xchg_op": "ms_xchg_op", "ms_p2p_op": "ms_p2p_op", "ms_jit_stats": "ms_jit_stats"}
@@ -391,6 +393,29 @@ def poseidon_prototypes():
     return prototypes(text[text.index("#define MINISTARK_HIP_POSEIDON_H"):])
 
 
+def render_hades_coin(protos):
+    """sys_hades_coin.rs: the entry points of include/ministark_hip_hades_coin.h (the Poseidon public coin of the 252-bit field), on sys.rs's types"""
+    lines = ["// GENERATED by scripts/gen_rust_sys.py from include/ministark_hip_hades_coin.h -- do not edit by hand.",
+             "// Raw bindings of the Poseidon public coin of the 252-bit field of libministark_hip.so (INTEGRATION.md section 3h).",
+             "#![allow(non_camel_case_types)]",
+             "use core::ffi::{c_int, c_uint, c_void};",
+             "use super::sys::ms_ctx;",
+             "",
+             "#[repr(C)] #[derive(Clone, Copy, Debug, Default)] pub struct ms_hades_coin_state { pub digest: [u64; 4], pub n_draws: u64, pub pad: [u32; 4] }",
+             "",
+             '#[link(name = "ministark_hip")]', 'extern "C" {']
+    for name, ret, plist in protos:
+        args = ", ".join(f"{(p + '_') if p in RUST_KEYWORDS else p}: {t}" for p, t in plist)
+        lines.append(f"    pub fn {name}({args})" + (f" -> {ret};" if ret else ";"))
+    lines += ["}", ""]
+    return "\n".join(lines)
+
+
+def hades_coin_prototypes():
+    text = open(HADES_COIN_HEADER).read()
+    return prototypes(text[text.index("#define MINISTARK_HIP_HADES_COIN_H"):])
+
+
 def main():
     protos = prototypes(open(HEADER).read())
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
@@ -437,6 +462,10 @@ def main():
     with open(POSEIDON_OUT, "w") as f:
         f.write(render_poseidon(protos))
     print(f"{len(protos)} prototypes -> {POSEIDON_OUT}")
+    protos = hades_coin_prototypes()
+    with open(HADES_COIN_OUT, "w") as f:
+        f.write(render_hades_coin(protos))
+    print(f"{len(protos)} prototypes -> {HADES_COIN_OUT}")
 
 
 if __name__ == "__main__":
