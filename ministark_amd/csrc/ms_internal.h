@@ -174,6 +174,7 @@ struct ms_ntt_plan {
     // remainder applied by pass 2 on its loads (ntt2_first_pass<.., UNI>, ntt2_mid_pass<.., LOADQ>)
     bool uni = false;
     uint64_t *d_tin4 = nullptr, *d_tout4 = nullptr;
+    uint64_t* d_lq = nullptr;            // pass 2 of such a plan with V = 1 and middle radix 256: the per-lane factor, one plain word per (block, k1)
     // two-pass coset LDE (lde2_kernels.h), built on first use on the forward plan of the LDE domain: per blow-up
     // [gpl | aux | t2] in one allocation
     struct Lde2 { unsigned log_b = 0; uint64_t *d = nullptr, *gpl = nullptr, *aux = nullptr, *t2 = nullptr, *tin4 = nullptr, *tout4 = nullptr, *c3 = nullptr; };

@@ -287,8 +287,8 @@ static int plan_build(ms_ctx* ctx, unsigned V, unsigned log_n, bool inverse_b, u
     // ... except the tables of the limb-form passes (ntt2_kernels.h): plain residues, four copies
     // {w, w 2^24, w 2^48, w 2^72} per twiddle, appended after the conversion
     size_t off_wr4[4] = {0, 0, 0, 0}, off_twu4[4] = {0, 0, 0, 0}, off_sc4 = 0, off_gp = 0, off_tin4 = 0, off_tout4 = 0;
-    bool has_wr4[4] = {false, false, false, false}, has_twu4[4] = {false, false, false, false}, has_gp = false, has_scu4 = false;
-    size_t off_scu4 = 0;
+    bool has_wr4[4] = {false, false, false, false}, has_twu4[4] = {false, false, false, false}, has_gp = false, has_scu4 = false, has_lq = false;
+    size_t off_scu4 = 0, off_lq = 0;
     p->uni = !p->small && p->npass == 3 && (p->lr[1] == 8 || p->lr[2] == 8) && p->lr[2] >= 6 && (n * V) % msntt2::TILE == 0;
     if (!p->small) {
         const uint64_t sh[4] = {1, (uint64_t)1 << 24, (uint64_t)1 << 48, gl::pow(2, 72)};
@@ -319,7 +319,8 @@ static int plan_build(ms_ctx* ctx, unsigned V, unsigned log_n, bool inverse_b, u
                     const uint64_t wu = gl::pow(ws, rU);
                     // UNI plans: pass 2 also carries h^j3 of the inter-pass factor (h w_n^k1)^(R3 j2 + j3), j3 = rev(U)
                     uint64_t x = (p->uni && q == 1 && !p->inverse && p->coset) ? gl::pow(h, rU) : 1;
-                    for (size_t k = 0; k < R; k++) { t[U * R + k] = x; x = gl::mul(x, wu); }
+                    // ntt2_mid_pass (radix 256) reads it in wave order: k = a' + 16 d sits at 16 a' + d, a wave's 16 factors of a round in a row
+                    for (size_t k = 0; k < R; k++) { t[U * R + (small_mid ? k : (k & 15) * 16 + (k >> 4))] = x; x = gl::mul(x, wu); }
                 }
                 off_twu4[q] = append4(t); has_twu4[q] = true;
             }
@@ -350,6 +351,20 @@ static int plan_build(ms_ctx* ctx, unsigned V, unsigned log_n, bool inverse_b, u
                 for (unsigned bp = 0; bp < 16; bp++) { t[(size_t)j2 * 16 + bp] = x; x = gl::mul(x, wm); }
             }
             off_tout4 = append4(t);
+            if (p->V == 1 && p->lr[1] == 8) {
+                // pass 2 (ntt2_mid_pass<.., PERM>): lq[U][k1] = w_n^(k1 rev(U)), the per-lane factor on its loads as one plain word
+                const unsigned nU = 1u << p->lr[2];              // blocks of 256 rows; a row is 2^log_s[1] = 256 words
+                t.resize((size_t)nU * 256);
+                for (unsigned U = 0; U < nU; U++) {
+                    unsigned rU = 0;
+                    for (unsigned f = 0; f < p->nfields[1]; f++)
+                        rU |= ((U >> p->fields[1][f].in_shift) & p->fields[1][f].mask) << p->fields[1][f].out_shift;
+                    const uint64_t wu = gl::pow(w, rU);
+                    uint64_t x = 1;
+                    for (unsigned k1 = 0; k1 < 256; k1++) { t[(size_t)U * 256 + k1] = x; x = gl::mul(x, wu); }
+                }
+                off_lq = append(t); has_lq = true;
+            }
         }
         if (!p->inverse && p->coset) { powers(t, 256, gl::pow(h, (uint64_t)(n >> 8))); off_gp = append4(t); has_gp = true; }
     }
@@ -375,6 +390,7 @@ static int plan_build(ms_ctx* ctx, unsigned V, unsigned log_n, bool inverse_b, u
         p->d_sc4 = p->d_tables + off_sc4;
         if (has_scu4) p->d_scu4 = p->d_tables + off_scu4;
         if (p->uni) { p->d_tin4 = p->d_tables + off_tin4; p->d_tout4 = p->d_tables + off_tout4; }
+        if (has_lq) p->d_lq = p->d_tables + off_lq;
         if (has_gp) p->d_g4 = p->d_tables + off_gp;
     }
     *out = p;
@@ -731,7 +747,7 @@ int plan_run(ms_ntt_plan* p, const void* const* src, void* const* dst, unsigned 
                 Q.wr4 = p->d_wr4[q]; Q.twu4 = p->d_twu4[q]; Q.sc4 = p->d_sc4; Q.scu4 = p->d_scu4; Q.g4 = p->d_g4;
                 Q.tw_lo = p->d_tw_lo; Q.tw_hi = p->d_tw_hi; Q.aux_lo = p->d_aux_lo; Q.aux_hi = p->d_aux_hi;
                 Q.log_n = p->log_n; Q.V = p->V; Q.valid_rows = valid_rows; Q.lo_bits = p->lo_bits; Q.log_s = p->log_s[q];
-                Q.tin4 = p->d_tin4; Q.tout4 = p->d_tout4; Q.r3 = p->lr[2];
+                Q.tin4 = p->d_tin4; Q.tout4 = p->d_tout4; Q.lq = p->d_lq; Q.r3 = p->lr[2];
                 // pass 1 of a uniform-factor plan with last radix 256 (four tiles per block of a row): XCD-aware tile order (ntt2_kernels.h)
                 Q.xcd_map = (q == 0 && p->uni && p->V == 1 && p->lr[2] == 8 && (n / msntt2::TILE) % 8 == 0) ? 1u : 0u;
                 Q.nfields = P.nfields;

@@ -21,6 +21,7 @@
 // Tile = 256 rows x 64 words = 16384 words per 512-thread workgroup, 32 words per lane.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "gl.h"
 #include "gl_dev.h"
 #include "gl_limb.h"
@@ -75,13 +76,15 @@ struct Params {
     uint64_t* dst[MAXC];
     // plain (non-Montgomery) tables of 4 pre-shifted copies: t[4 e + i] = w^e * 2^(24 i) mod p
     const uint64_t* wr4;       // w_256^e, e < 256                      (between the two networks)
-    const uint64_t* twu4;      // middle pass: [U][k], w_n^((rev(U) k) << log_s)   (after the second network)
+    const uint64_t* twu4;      // middle pass: [U][k], w_n^((rev(U) k) << log_s)   (after the second network); the radix-256 pass
+                               // (ntt2_mid_pass) has it in wave order, k = a' + 16 d at [U][16 a' + d]
     const uint64_t* sc4;       // last pass, SCALE 1: the constant n^-1 (4 copies)
     const uint64_t* scu4;      // last pass, SCALE 2: [k] h^-(k 2^log_s), k < 256 (4 copies): the row part of the coset scale
     const uint64_t* g4;        // pass 1 coset: g^j1, j1 < 256 (4 copies; the product on the loads uses three)
     // uniform inter-pass factor of a three-pass plan (UNI kernels, see ntt2_first_pass):
     const uint64_t* tin4;      // pass 1: [j2][b][a'] w_256^(a' b) w_n^(a' R3 j2)            (between the two networks)
     const uint64_t* tout4;     // pass 1: [j2][b'] h^(R3 j2) w_n^(16 b' R3 j2)                (after the second network)
+    const uint64_t* lq;        // pass 2, radix 256, V = 1: [U][k1] w_n^(k1 rev(U)), one plain word each (ntt2_mid_pass<.., PERM>'s factor on the loads)
     // Montgomery-form tables of the round-1 kernels (per-lane twiddles of pass 1, scale walk of the last pass)
     const uint64_t* tw_lo;
     const uint64_t* tw_hi;
@@ -171,6 +174,18 @@ MS_HD unsigned spin(unsigned x) { return x; }
 
 using gld::wave_lockstep;
 
+// The lane's index, computed where it is asked for (two instructions, no input register).  The radix-256 middle pass holds 64
+// loaded words and a network in limb form at once: a lane index kept from the top of the kernel is spilled there.
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ unsigned lane_here() {
+    unsigned l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+#else
+MS_HD unsigned lane_here() { return threadIdx.x & 63; }
+#endif
+
 // run index g of a middle pass (log_s = 8) -> block U of R rows and the run q of 64 words inside a row of 256 V words.  PERM kernels
 // are V = 1 (four runs per row): shifts; otherwise one uniform division by the run count 4 V
 template <bool PERM>
@@ -196,11 +211,16 @@ __device__ __forceinline__ glimb::Q3 q3_at(const uint64_t* t, unsigned slot) {
 }
 
 // first network of a pass: 16 loaded words (rows 16 a + b) -> w_256^(a' b) * DFT16, as weak 64-bit residues
-//   IN   0: words as they are; 1: times the wave-uniform g4[16 a + b] (coset, pass 1); 2: times the per-lane q
-//        (both as glimb::mul3_to_limbs: three pre-shifted copies of the factor, no reduction between product and network)
+//   IN   0: words as they are; 1: times the wave-uniform g4[16 a + b] (coset, pass 1: glimb::mul3_to_limbs, three pre-shifted
+//        copies of the factor in scalar registers); 2: times the per-lane q, no reduction between product and network either way:
+//        QF = uint64_t  one plain word, glimb::mul_to_limbs.  The factor costs 2 vector registers instead of 6, which is what
+//                       ends the spills of ntt2_mid_pass<.., LOADQ>; its limbs are signed, |l_i| < 2^24, which is what
+//                       glimb::dft takes: the outputs swing by < 2^28.2 around the bias 2^29 - 32, so they stay inside
+//                       (2^29 - 2^28.2, 2^29 + 2^28.2), a subset of mul_fold_co's [0, 2^30).
+//        QF = Q3        three pre-shifted copies in vector registers, glimb::mul3_to_limbs (non-negative limbs)
 //   UNI  the factor after the network comes from tin4 at slot tslot + a' (pass 1 of a three-pass plan) instead of wr4
-template <bool INV, int NA, int IN, bool UNI = false>
-__device__ __forceinline__ void net1(uint64_t* x, const Params& P, unsigned b, const glimb::Q3& q = glimb::Q3{}, unsigned tslot = 0) {
+template <bool INV, int NA, int IN, bool UNI = false, class QF = uint64_t>
+__device__ __forceinline__ void net1(uint64_t* x, const Params& P, unsigned b, const QF& q = QF{}, unsigned tslot = 0) {
     glimb::L4 v[16];
     if constexpr (IN == 1) {
         #pragma unroll
@@ -216,8 +236,10 @@ __device__ __forceinline__ void net1(uint64_t* x, const Params& P, unsigned b, c
     } else {
         #pragma unroll
         for (int a = 0; a < NA; a++) {
-            if constexpr (IN == 2) v[a] = glimb::mul3_to_limbs(x[a], q);
-            else v[a] = glimb::from_u64(x[a]);
+            if constexpr (IN == 2) {
+                if constexpr (std::is_same<QF, uint64_t>::value) v[a] = glimb::mul_to_limbs(x[a], q);
+                else v[a] = glimb::mul3_to_limbs(x[a], q);
+            } else v[a] = glimb::from_u64(x[a]);
         }
     }
     auto tw = [&](int c) { return UNI ? w4_at(P.tin4, tslot + c) : w4_at(P.wr4, (b * c) & 255); };
@@ -252,7 +274,9 @@ __device__ __forceinline__ void net1(uint64_t* x, const Params& P, unsigned b, c
 // LOADQ (pass 2 of a three-pass plan whose pass 1 is the UNI kernel): every word is multiplied on the way in by
 //   w_n^(k1 j3), k1 = the lane's position in the row, j3 = this tile's block -- the part of the inter-pass factor
 //   (h w_n^k1)^(R3 j2 + j3) that pass 1 cannot apply with wave-uniform operands.  It is one value per lane and tile,
-//   so the 128-bit product replaces the plain conversion to limbs (no running product; h^j3 sits in twu4).
+//   so the 128-bit product replaces the plain conversion to limbs (no running product; h^j3 sits in twu4).  With V = 1 (PERM)
+//   the factor is read ready-made from lq (one 8-byte load per lane); otherwise it is built from tw_lo / tw_hi (two gathers
+//   and two Montgomery products).
 // PERM (with LOADQ, V = 1): pass 1 left every 256-word row in the order its stores like best (see
 //   ntt2_first_pass<.., PERM>): k1 = a' + 16 d sits at 64 (d >> 2) + 32 ((d >> 1) & 1) + 16 (a' >> 3) + 2 (a' & 7) + (d & 1),
 //   a permutation INSIDE each run of 64 words.  The 64 words k1 = 64 q + lane of this tile are therefore this tile's own four
@@ -268,8 +292,8 @@ __global__ void __launch_bounds__(NT, 4) ntt2_mid_pass(Params P) {
     const size_t sw = ((size_t)1 << P.log_s) * P.V;
     const unsigned tiles_per_u = (unsigned)(sw / TW);
     const unsigned U = NTT2_BX / tiles_per_u;
-    const size_t base = (size_t)U * 256 * sw + (size_t)(NTT2_BX % tiles_per_u) * TW + lane;
-    size_t rbase = base;
+    const size_t base0 = (size_t)U * 256 * sw + (size_t)(NTT2_BX % tiles_per_u) * TW;
+    size_t rbase = base0 + lane;
     if constexpr (PERM) {       // natural k1 = 64 q + lane sits at 64 q + pi(lane): inside this tile's own 64 words, so dst may be src
         const unsigned q = NTT2_BX % tiles_per_u;
         rbase = (size_t)U * 256 * sw + 64 * q + ((lane >> 5) & 1) * 32 + ((lane >> 3) & 1) * 16 + (lane & 7) * 2 + ((lane >> 4) & 1);
@@ -295,34 +319,36 @@ __global__ void __launch_bounds__(NT, 4) ntt2_mid_pass(Params P) {
         qlo = P.aux_lo[e & ((1u << P.lo_bits) - 1)];
         qhi = P.aux_hi[e >> P.lo_bits];
     }
-    if constexpr (LOADQ) {                                   // the two table words of w_n^(k1 j3) first: they come back before the
+    uint64_t qpl = 0;
+    if constexpr (LOADQ && PERM) {                           // V = 1: the plain factor itself, lq[U][k1] -- one coalesced 512-byte read per wave,
+        qpl = P.lq[U * 256 + (NTT2_BX % tiles_per_u) * TW + lane];                    // the same 512 bytes for all 8 waves of the tile
+    } else if constexpr (LOADQ) {                            // the two table words of w_n^(k1 j3) first: they come back before the
         const unsigned k1 = ((NTT2_BX % tiles_per_u) * TW + lane) / P.V;              // tile's words and are combined meanwhile
         const uint64_t e = (uint64_t)k1 * digit_rev(P, U);
         qlo = P.tw_lo[e & ((1u << P.lo_bits) - 1)];
         qhi = P.tw_hi[e >> P.lo_bits];
     }
     load_half(0); load_half(1);
-    glimb::Q3 qpl{};
-    if constexpr (LOADQ || SCALE == 2) {                     // three plain copies q 2^(24 i): the data keeps its own Montgomery factor
-        const uint64_t qm = gld::mmul(qlo, qhi);
-        qpl = glimb::q3_from(gld::mmul(qm, 1), gld::mmul(qm, (uint64_t)1 << 24), gld::mmul(qm, (uint64_t)1 << 48));
-    }
+    if constexpr ((LOADQ && !PERM) || SCALE == 2) qpl = gld::mmul(gld::mmul(qlo, qhi), 1);      // one plain word: the data keeps its own Montgomery factor
     #pragma unroll
     for (int h = 0; h < 2; h++) {
         net1<INV, 16, (LOADQ || SCALE == 2) ? 2 : 0>(x[h], P, w + 8 * h, qpl);
+        const unsigned ln = LOADQ ? lane_here() : lane;
         #pragma unroll
-        for (int j = 0; j < 8; j++) xch[((w + 8 * h) * 8 + j) * TW + lane] = x[h][j];
+        for (int j = 0; j < 8; j++) xch[((w + 8 * h) * 8 + j) * TW + ln] = x[h][j];
         __builtin_amdgcn_sched_barrier(0);
     }
 
     // exchange: (wave, h) = b, register a'  ->  (wave, h) = a', register b; the lane keeps its word.
     // Round r moves the registers a' in [8r, 8r + 8) and is followed by the second network of h = r.
+    glimb::W4 wn[4];
     #pragma unroll
     for (int r = 0; r < 2; r++) {
         __syncthreads();
+        const unsigned ln = LOADQ ? lane_here() : lane;
         uint64_t y[16];
         #pragma unroll
-        for (int b = 0; b < 16; b++) y[b] = xch[(b * 8 + w) * TW + lane];
+        for (int b = 0; b < 16; b++) y[b] = xch[(b * 8 + w) * TW + ln];
         if (r == 0) {
             // the second half of the first networks' results moves to LDS as soon as everybody has read round 0 -- BEFORE
             // this round's network, so that the 32 registers it occupied are free while the network runs
@@ -330,29 +356,25 @@ __global__ void __launch_bounds__(NT, 4) ntt2_mid_pass(Params P) {
             #pragma unroll
             for (int h = 0; h < 2; h++)
                 #pragma unroll
-                for (int j = 0; j < 8; j++) xch[((w + 8 * h) * 8 + j) * TW + lane] = x[h][8 + j];
+                for (int j = 0; j < 8; j++) xch[((w + 8 * h) * 8 + j) * TW + ln] = x[h][8 + j];
         }
         const unsigned ap = w + 8 * r;                        // a'
-        glimb::W4 wn[4];                                      // twiddles one group ahead of their use (scalar loads from a 2 MiB table)
-        if constexpr (!LAST) {
-            #pragma unroll
-            for (int j = 0; j < 4; j++) wn[j] = w4_at(P.twu4, U * 256 + ap + 16 * j);
-        }
+        // twiddles one group ahead of their use: twu4 is [U][a'][d] here, so the four factors d = 4 g .. 4 g + 3 of a group are one
+        // 128-byte line (two s_load_dwordx16) and the 16 of a wave and round 512 contiguous bytes of a 2 MiB table
+        if constexpr (!LAST) { if (r == 0) w4x4_at(P.twu4, U * 256 + ap * 16, wn); }
         glimb::L4 v[16];
         #pragma unroll
         for (int b = 0; b < 16; b++) v[b] = glimb::from_u64(y[b]);
         glimb::dft<16, INV>(v);
-        size_t pos = base + (size_t)ap * sw;
+        size_t pos = base0 + ln + (size_t)ap * sw;
         #pragma unroll
         for (int g = 0; g < 4; g++) {
             glimb::W4 wc[4];
             if constexpr (!LAST) {
                 #pragma unroll
                 for (int j = 0; j < 4; j++) wc[j] = wn[j];
-                if (g < 3) {
-                    #pragma unroll
-                    for (int j = 0; j < 4; j++) wn[j] = w4_at(P.twu4, U * 256 + ap + 16 * (4 * (g + 1) + j));
-                }
+                if (g < 3) w4x4_at(P.twu4, U * 256 + ap * 16 + 4 * (g + 1), wn);
+                else if (r == 0) w4x4_at(P.twu4, U * 256 + (ap + 8) * 16, wn);      // round 1's first group, before this round's last stores go out
                 __builtin_amdgcn_sched_barrier(0);
             }
             #pragma unroll
@@ -484,7 +506,7 @@ __global__ void __launch_bounds__(NT, 4) ntt2_mid_pass_r(Params P) {
     for (int h = 0; h < 2; h++) {
         const unsigned b = (w + 8 * h) % T2;
         const uint64_t qm = gld::mmul(qlo[h], qhi[h]);
-        const glimb::Q3 qpl = glimb::q3_from(gld::mmul(qm, 1), gld::mmul(qm, (uint64_t)1 << 24), gld::mmul(qm, (uint64_t)1 << 48));
+        const uint64_t qpl = gld::mmul(qm, 1);
         net1<INV, 16, 2>(x[h], P, b, qpl);                    // the factor after the network: wr4 = w_R^e here, slot a' b < R
         #pragma unroll
         for (int j = 0; j < 8; j++) xch[((w + 8 * h) * 8 + j) * TW + lane] = x[h][j];
@@ -663,7 +685,7 @@ __global__ void __launch_bounds__(NT, 4) ntt2_first_pass(Params P) {
     load_half(0); load_half(1);          // both halves in flight before the first network (no spills since round 2b)
     #pragma unroll
     for (int h = 0; h < 2; h++) {
-        net1<INV, NA, COSET ? 1 : 0, UNI>(x[h], P, w + 8 * h, glimb::Q3{}, (j2 * 16 + w + 8 * h) * 16);
+        net1<INV, NA, COSET ? 1 : 0, UNI>(x[h], P, w + 8 * h, (uint64_t)0, (j2 * 16 + w + 8 * h) * 16);
         #pragma unroll
         for (int j = 0; j < 8; j++) xch[((w + 8 * h) * 8 + j) * XPITCH + lane] = x[h][j];
         __builtin_amdgcn_sched_barrier(0);

@@ -66,6 +66,7 @@ int main(int argc, char** argv) {
     uint64_t* aux_lo = dev_table(4096, 7); uint64_t* aux_hi = dev_table(4096, 8);
     msntt2::Params Q; memset(&Q, 0, sizeof Q);
     Q.wr4 = wr4; Q.twu4 = twu4; Q.sc4 = sc4; Q.g4 = gp; Q.tw_lo = tw_lo; Q.tw_hi = tw_hi; Q.aux_lo = aux_lo; Q.aux_hi = aux_hi;
+    Q.lq = dev_table((size_t)256 * 256, 13);      // pass 2's per-lane factor, one word per (block, k1)
     Q.log_n = log_n; Q.V = 1; Q.valid_rows = 256; Q.lo_bits = 12; Q.tin4 = tin4; Q.tout4 = tout4; Q.r3 = 8;
 #ifdef VAR_XCD
     Q.xcd_map = 1;
