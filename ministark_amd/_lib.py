@@ -215,20 +215,24 @@ class Lib:
         logup_sigs = {
             "ms_build_logup_columns": (i, [vp, i, i, sz, c_void_pp, u, vp, u, vp, vp, vp, u, c_void_pp]),
         }
-        # include/ministark_hip_rpo_coin.h: the RPO-256 public coin (each the twin of its ms_coin_* namesake, minus `hash`)
-        rpo_coin_sigs = {
-            "ms_rpo_coin_create": (i, [vp, vp, c_void_pp]),
-            "ms_rpo_coin_destroy": (i, [vp, vp]),
-            "ms_rpo_coin_read": (i, [vp, vp, vp]),
-            "ms_rpo_coin_write": (i, [vp, vp, vp]),
-            "ms_rpo_coin_reseed_digest": (i, [vp, vp, vp]),
-            "ms_rpo_coin_reseed_int": (i, [vp, vp, ctypes.c_uint64]),
-            "ms_rpo_coin_reseed_elements": (i, [vp, vp, i, vp, sz]),
-            "ms_rpo_coin_reseed_elements_host": (i, [vp, vp, i, vp, sz]),
-            "ms_rpo_coin_draw": (i, [vp, vp, i, sz, vp]),
-            "ms_rpo_coin_draw_queries": (i, [vp, vp, sz, sz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(sz)]),
-            "ms_rpo_coin_pow_grind": (i, [vp, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
-        }
+        # include/ministark_hip_rpo_coin.h and include/ministark_hip_hades_coin.h: the two algebraic public coins, each entry point the twin of its
+        # ms_coin_* namesake, minus `hash`
+        def algebraic_coin_sigs(prefix):
+            return {prefix + name: sig for name, sig in {
+                "create": (i, [vp, vp, c_void_pp]),
+                "destroy": (i, [vp, vp]),
+                "read": (i, [vp, vp, vp]),
+                "write": (i, [vp, vp, vp]),
+                "reseed_digest": (i, [vp, vp, vp]),
+                "reseed_int": (i, [vp, vp, ctypes.c_uint64]),
+                "reseed_elements": (i, [vp, vp, i, vp, sz]),
+                "reseed_elements_host": (i, [vp, vp, i, vp, sz]),
+                "draw": (i, [vp, vp, i, sz, vp]),
+                "draw_queries": (i, [vp, vp, sz, sz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(sz)]),
+                "pow_grind": (i, [vp, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+            }.items()}
+        rpo_coin_sigs = algebraic_coin_sigs("ms_rpo_coin_")
+        hades_coin_sigs = algebraic_coin_sigs("ms_hades_coin_")
         # include/ministark_hip_lookup.h: the multiplicity column of a LogUp lookup, counted on the device
         lookup_sigs = {
             "ms_lookup_multiplicities": (i, [vp, i, sz, c_void_pp, u, u, vp, vp, u, vp, vp]),
@@ -253,20 +257,6 @@ class Lib:
             "ms_poseidon252_rows": (i, [vp, sz, c_void_pp, u, vp]),
             "ms_poseidon252_rows_row_major": (i, [vp, sz, u, vp, vp]),
             "ms_poseidon252_merkle": (i, [vp, sz, vp, vp]),
-        }
-        # include/ministark_hip_hades_coin.h: the Poseidon public coin of the 252-bit field (each the twin of its ms_rpo_coin_* namesake)
-        hades_coin_sigs = {
-            "ms_hades_coin_create": (i, [vp, vp, c_void_pp]),
-            "ms_hades_coin_destroy": (i, [vp, vp]),
-            "ms_hades_coin_read": (i, [vp, vp, vp]),
-            "ms_hades_coin_write": (i, [vp, vp, vp]),
-            "ms_hades_coin_reseed_digest": (i, [vp, vp, vp]),
-            "ms_hades_coin_reseed_int": (i, [vp, vp, ctypes.c_uint64]),
-            "ms_hades_coin_reseed_elements": (i, [vp, vp, i, vp, sz]),
-            "ms_hades_coin_reseed_elements_host": (i, [vp, vp, i, vp, sz]),
-            "ms_hades_coin_draw": (i, [vp, vp, i, sz, vp]),
-            "ms_hades_coin_draw_queries": (i, [vp, vp, sz, sz, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(sz)]),
-            "ms_hades_coin_pow_grind": (i, [vp, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         }
         self.optional = {}
         for name, (res, args) in (list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items())

@@ -15,8 +15,77 @@ from .api import F252_P, FIELD_WORDS, GL_P, DeviceBytes, GpuVec, f252_from_mont_
 HASH_IDS = {"sha256": 0, "blake2s": 1, "keccak256": 3, "sha3_256": 4}        # 2 stays unknown: the RPO-256 coin is RpoCoin, a family of its own
 
 
-class PublicCoin:
+class _Coin:
+    """What the three coins share: every method is the entry point `_prefix` + its name on the coin's handle, so `pipeline.prove` holds
+    any of them.  A subclass creates the coin (`_create`) and knows its state struct (`state`, `set_state`)."""
+
+    _prefix = None                                                              # "ms_coin_", "ms_rpo_coin_", "ms_hades_coin_"
+
+    ptr = None                                                                  # until `_create` has returned, and after `close`
+
+    def _create(self, planner, *args):
+        self.planner = planner
+        h = ctypes.c_void_p()
+        planner.lib.check(getattr(planner.lib, self._prefix + "create")(planner.handle, *args, ctypes.byref(h)))
+        self.ptr = h.value
+
+    def _call(self, name, *args):
+        self.planner.lib.check(getattr(self.planner.lib, self._prefix + name)(self.planner.handle, self.ptr, *args))
+
+    def reseed_digest(self, digest):
+        """`reseed_with_digest`: digest is a DeviceBytes (its first 32 bytes) or a device address, e.g. `tree.root_ptr()`.  Asynchronous."""
+        self._call("reseed_digest", digest.ptr if isinstance(digest, DeviceBytes) else int(digest))
+
+    def reseed_int(self, value):
+        """`reseed_with_int` (the proof-of-work nonce).  Asynchronous."""
+        self._call("reseed_int", int(value))
+
+    def reseed_elements(self, elems, field=None):
+        """`reseed_with_field_elements`: a GpuVec, or numpy u64 Montgomery words of `field` elements on the host.  Asynchronous."""
+        if isinstance(elems, GpuVec):
+            self._call("reseed_elements", elems.field, elems.ptr, len(elems))
+            return
+        if field is None:
+            raise ValueError("reseed_elements: host elements need their field")
+        arr = np.ascontiguousarray(elems, dtype=np.uint64).ravel()
+        assert arr.size % FIELD_WORDS[field] == 0
+        self._call("reseed_elements_host", field, arr.ctypes.data, arr.size // FIELD_WORDS[field])
+
+    def draw(self, field, count=1):
+        """`draw()` x count -> GpuVec of `count` elements of `field` (Montgomery form), left on the device.  Asynchronous."""
+        out = GpuVec(self.planner, count, field)
+        self._call("draw", field, count, out.ptr)
+        return out
+
+    def draw_queries(self, max_n, domain_size):
+        """`draw_queries(max_n, domain_size)`: the distinct positions in ascending order.  Blocks."""
+        pos = np.empty(max(max_n, 1), dtype=np.uint64)
+        n = ctypes.c_size_t(0)
+        self._call("draw_queries", max_n, domain_size, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(n))
+        return [int(p) for p in pos[: n.value]]
+
+    def grind(self, bits, max_nonce=1 << 40):
+        """`grind_proof_of_work(bits)`: the smallest nonce >= 1; the coin is not reseeded (channel.rs:86-93 does that).  Blocks."""
+        out = ctypes.c_uint64(0)
+        self._call("pow_grind", bits, max_nonce, ctypes.byref(out))
+        return out.value
+
+    def close(self):
+        if self.ptr and self.planner.handle:
+            getattr(self.planner.lib, self._prefix + "destroy")(self.planner.handle, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PublicCoin(_Coin):
     """`PublicCoin::new(seed)` (src/random.rs:102-109).  seed32: 32 bytes; hash: "sha256" (Sha256HashFn), "blake2s", "keccak256" or "sha3_256"."""
+
+    _prefix = "ms_coin_"
 
     def __init__(self, planner, seed32, hash="sha256"):
         if hash not in HASH_IDS:
@@ -24,57 +93,13 @@ class PublicCoin:
         seed32 = bytes(seed32)
         if len(seed32) != 32:
             raise ValueError("the coin's seed is a 32-byte digest")
-        self.planner, self.hash = planner, hash
-        h = ctypes.c_void_p()
-        planner.lib.check(planner.lib.ms_coin_create(planner.handle, HASH_IDS[hash], ctypes.create_string_buffer(seed32, 32), ctypes.byref(h)))
-        self.ptr = h.value
-
-    def _call(self, fn, *args):
-        self.planner.lib.check(fn(self.planner.handle, self.ptr, *args))
-
-    def reseed_digest(self, digest):
-        """`reseed_with_digest`: digest is a DeviceBytes (its first 32 bytes) or a device address, e.g. `tree.root_ptr()`.  Asynchronous."""
-        self._call(self.planner.lib.ms_coin_reseed_digest, digest.ptr if isinstance(digest, DeviceBytes) else int(digest))
-
-    def reseed_int(self, value):
-        """`reseed_with_int` (the proof-of-work nonce).  Asynchronous."""
-        self._call(self.planner.lib.ms_coin_reseed_int, int(value))
-
-    def reseed_elements(self, elems, field=None):
-        """`reseed_with_field_elements`: a GpuVec, or numpy u64 Montgomery words of `field` elements on the host.  Asynchronous."""
-        L = self.planner.lib
-        if isinstance(elems, GpuVec):
-            self._call(L.ms_coin_reseed_elements, elems.field, elems.ptr, len(elems))
-            return
-        if field is None:
-            raise ValueError("reseed_elements: host elements need their field")
-        arr = np.ascontiguousarray(elems, dtype=np.uint64).ravel()
-        assert arr.size % FIELD_WORDS[field] == 0
-        self._call(L.ms_coin_reseed_elements_host, field, arr.ctypes.data, arr.size // FIELD_WORDS[field])
-
-    def draw(self, field, count=1):
-        """`draw()` x count -> GpuVec of `count` elements of `field` (Montgomery form), left on the device.  Asynchronous."""
-        out = GpuVec(self.planner, count, field)
-        self._call(self.planner.lib.ms_coin_draw, field, count, out.ptr)
-        return out
-
-    def draw_queries(self, max_n, domain_size):
-        """`draw_queries(max_n, domain_size)`: the distinct positions in ascending order.  Blocks."""
-        pos = np.empty(max(max_n, 1), dtype=np.uint64)
-        n = ctypes.c_size_t(0)
-        self._call(self.planner.lib.ms_coin_draw_queries, max_n, domain_size, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(n))
-        return [int(p) for p in pos[: n.value]]
-
-    def grind(self, bits, max_nonce=1 << 40):
-        """`grind_proof_of_work(bits)`: the smallest nonce >= 1; the coin is not reseeded (channel.rs:86-93 does that).  Blocks."""
-        out = ctypes.c_uint64(0)
-        self._call(self.planner.lib.ms_coin_pow_grind, bits, max_nonce, ctypes.byref(out))
-        return out.value
+        self.hash = hash
+        self._create(planner, HASH_IDS[hash], ctypes.create_string_buffer(seed32, 32))
 
     def state(self):
         """-> dict(seed=bytes, counter=int, unread=bytes): the unread bytes are consumed from the end.  Blocks."""
         st = _lib.CoinState()
-        self._call(self.planner.lib.ms_coin_read, ctypes.byref(st))
+        self._call("read", ctypes.byref(st))
         return {"seed": bytes(st.seed), "counter": int(st.counter), "unread": bytes(st.bytes)[: st.nbytes]}
 
     def set_state(self, seed, counter, unread=b""):
@@ -83,18 +108,7 @@ class PublicCoin:
         ctypes.memmove(st.seed, bytes(seed), 32)
         st.counter, st.nbytes = counter, len(unread)
         ctypes.memmove(st.bytes, bytes(unread).ljust(32, b"\0"), 32)
-        self._call(self.planner.lib.ms_coin_write, ctypes.byref(st))
-
-    def close(self):
-        if self.ptr and self.planner.handle:
-            self.planner.lib.ms_coin_destroy(self.planner.handle, self.ptr)
-        self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("write", ctypes.byref(st))
 
 
 def rpo_seed(seed):
@@ -113,67 +127,23 @@ def rpo_seed(seed):
     return words
 
 
-class RpoCoin:
+class RpoCoin(_Coin):
     """The RPO-256 public coin (ms_rpo_coin_*): a 12-element sponge on the device, capacity s[0..4), rate s[4..12).  It has `PublicCoin`'s
-    methods, so `pipeline.prove` holds either.  seed: see `rpo_seed`.  The rules are in include/ministark_hip_rpo_coin.h."""
+    methods, so `pipeline.prove` holds either.  seed: see `rpo_seed`.  The rules are in include/ministark_hip_rpo_coin.h: `reseed_digest`
+    absorbs four elements of device memory (the root of an RPO-256 tree), `reseed_int` a u64 as its two 32-bit halves, `reseed_elements`
+    and `draw` work over Fp or Fq3, `draw_queries` takes a power of two up to 2^32, and `grind` finds the smallest nonce >= 1 after whose
+    `reseed_int` s[0] has its low `bits` bits zero."""
 
     hash = "rpo256"
+    _prefix = "ms_rpo_coin_"
 
     def __init__(self, planner, seed):
-        self.planner, self.ptr = planner, None
-        words = rpo_seed(seed)
-        h = ctypes.c_void_p()
-        buf = (ctypes.c_uint64 * 4)(*[gl_to_mont(w) for w in words])
-        planner.lib.check(planner.lib.ms_rpo_coin_create(planner.handle, buf, ctypes.byref(h)))
-        self.ptr = h.value
-
-    def _call(self, fn, *args):
-        self.planner.lib.check(fn(self.planner.handle, self.ptr, *args))
-
-    def reseed_digest(self, digest):
-        """Absorb four elements of device memory: a DeviceBytes (its first 32 bytes) or a device address, e.g. `tree.root_ptr()` of an
-        RPO-256 tree.  Asynchronous."""
-        self._call(self.planner.lib.ms_rpo_coin_reseed_digest, digest.ptr if isinstance(digest, DeviceBytes) else int(digest))
-
-    def reseed_int(self, value):
-        """Absorb a u64 as its two 32-bit halves (the proof-of-work nonce).  Asynchronous."""
-        self._call(self.planner.lib.ms_rpo_coin_reseed_int, int(value))
-
-    def reseed_elements(self, elems, field=None):
-        """Absorb field elements: a GpuVec, or numpy u64 Montgomery words of `field` (Fp or Fq3) elements on the host.  Asynchronous."""
-        L = self.planner.lib
-        if isinstance(elems, GpuVec):
-            self._call(L.ms_rpo_coin_reseed_elements, elems.field, elems.ptr, len(elems))
-            return
-        if field is None:
-            raise ValueError("reseed_elements: host elements need their field")
-        arr = np.ascontiguousarray(elems, dtype=np.uint64).ravel()
-        assert arr.size % FIELD_WORDS[field] == 0
-        self._call(L.ms_rpo_coin_reseed_elements_host, field, arr.ctypes.data, arr.size // FIELD_WORDS[field])
-
-    def draw(self, field, count=1):
-        """-> GpuVec of `count` elements of `field` (Fp or Fq3, Montgomery form), left on the device.  Asynchronous."""
-        out = GpuVec(self.planner, count, field)
-        self._call(self.planner.lib.ms_rpo_coin_draw, field, count, out.ptr)
-        return out
-
-    def draw_queries(self, max_n, domain_size):
-        """The distinct positions in ascending order; domain_size is a power of two up to 2^32.  Blocks."""
-        pos = np.empty(max(max_n, 1), dtype=np.uint64)
-        n = ctypes.c_size_t(0)
-        self._call(self.planner.lib.ms_rpo_coin_draw_queries, max_n, domain_size, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(n))
-        return [int(p) for p in pos[: n.value]]
-
-    def grind(self, bits, max_nonce=1 << 40):
-        """The smallest nonce >= 1 after whose `reseed_int` s[0] has its low `bits` bits zero; the coin is not reseeded.  Blocks."""
-        out = ctypes.c_uint64(0)
-        self._call(self.planner.lib.ms_rpo_coin_pow_grind, bits, max_nonce, ctypes.byref(out))
-        return out.value
+        self._create(planner, (ctypes.c_uint64 * 4)(*[gl_to_mont(w) for w in rpo_seed(seed)]))
 
     def state(self):
         """-> {"s": the 12 state elements as canonical integers, "pos": the next unread rate element (12: none)}.  Blocks."""
         st = _lib.RpoCoinState()
-        self._call(self.planner.lib.ms_rpo_coin_read, ctypes.byref(st))
+        self._call("read", ctypes.byref(st))
         return {"s": [gl_from_mont(int(w)) for w in st.s], "pos": int(st.pos)}
 
     def set_state(self, s, pos):
@@ -182,18 +152,7 @@ class RpoCoin:
         for k, v in enumerate(s):
             st.s[k] = gl_to_mont(int(v))
         st.pos = pos
-        self._call(self.planner.lib.ms_rpo_coin_write, ctypes.byref(st))
-
-    def close(self):
-        if self.ptr and self.planner.handle:
-            self.planner.lib.ms_rpo_coin_destroy(self.planner.handle, self.ptr)
-        self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("write", ctypes.byref(st))
 
 
 def poseidon_seed(seed):
@@ -210,68 +169,25 @@ def poseidon_seed(seed):
     return value
 
 
-class PoseidonCoin:
+class PoseidonCoin(_Coin):
     """The Poseidon public coin of the 252-bit field (ms_hades_coin_*): one field element and a draw counter on the device.  It has
     `RpoCoin`'s methods, so `pipeline.prove` holds either.  seed: see `poseidon_seed`.  The rules are in
-    include/ministark_hip_hades_coin.h: digest = hash2(digest, x) absorbs, permute(digest, n_draws + i, 3)[0] draws, tag 4 grinds."""
+    include/ministark_hip_hades_coin.h: digest = hash2(digest, x) absorbs, permute(digest, n_draws + i, 3)[0] draws, tag 4 grinds.
+    `reseed_digest` absorbs one element of device memory (the root of a "poseidon252" tree), `reseed_int` a u64, `reseed_elements` the
+    hash_many of STARK252_FP elements; `draw` gives STARK252_FP elements, `draw_queries` takes a power of two up to 2^32, and `grind`
+    finds the smallest nonce n >= 1 such that permute(digest, n, 4)[0] has its low `bits` bits zero."""
 
     hash = "poseidon252"
+    _prefix = "ms_hades_coin_"
 
     def __init__(self, planner, seed):
-        self.planner, self.ptr = planner, None
         value = poseidon_seed(seed)
-        h = ctypes.c_void_p()
-        buf = (ctypes.c_uint64 * 4)(*[(value >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)])      # canonical words: the library converts
-        planner.lib.check(planner.lib.ms_hades_coin_create(planner.handle, buf, ctypes.byref(h)))
-        self.ptr = h.value
-
-    def _call(self, fn, *args):
-        self.planner.lib.check(fn(self.planner.handle, self.ptr, *args))
-
-    def reseed_digest(self, digest):
-        """Absorb one element of device memory: a DeviceBytes (its first 32 bytes) or a device address, e.g. `tree.root_ptr()` of a
-        "poseidon252" tree.  Asynchronous."""
-        self._call(self.planner.lib.ms_hades_coin_reseed_digest, digest.ptr if isinstance(digest, DeviceBytes) else int(digest))
-
-    def reseed_int(self, value):
-        """Absorb a u64 (the proof-of-work nonce).  Asynchronous."""
-        self._call(self.planner.lib.ms_hades_coin_reseed_int, int(value))
-
-    def reseed_elements(self, elems, field=None):
-        """Absorb hash_many of field elements: a GpuVec, or numpy u64 Montgomery words of STARK252_FP elements on the host.  Asynchronous."""
-        L = self.planner.lib
-        if isinstance(elems, GpuVec):
-            self._call(L.ms_hades_coin_reseed_elements, elems.field, elems.ptr, len(elems))
-            return
-        if field is None:
-            raise ValueError("reseed_elements: host elements need their field")
-        arr = np.ascontiguousarray(elems, dtype=np.uint64).ravel()
-        assert arr.size % FIELD_WORDS[field] == 0
-        self._call(L.ms_hades_coin_reseed_elements_host, field, arr.ctypes.data, arr.size // FIELD_WORDS[field])
-
-    def draw(self, field, count=1):
-        """-> GpuVec of `count` elements of STARK252_FP (Montgomery form), left on the device.  Asynchronous."""
-        out = GpuVec(self.planner, count, field)
-        self._call(self.planner.lib.ms_hades_coin_draw, field, count, out.ptr)
-        return out
-
-    def draw_queries(self, max_n, domain_size):
-        """The distinct positions in ascending order; domain_size is a power of two up to 2^32.  Blocks."""
-        pos = np.empty(max(max_n, 1), dtype=np.uint64)
-        n = ctypes.c_size_t(0)
-        self._call(self.planner.lib.ms_hades_coin_draw_queries, max_n, domain_size, pos.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(n))
-        return [int(p) for p in pos[: n.value]]
-
-    def grind(self, bits, max_nonce=1 << 40):
-        """The smallest nonce n >= 1 such that permute(digest, n, 4)[0] has its low `bits` bits zero; the coin is not reseeded.  Blocks."""
-        out = ctypes.c_uint64(0)
-        self._call(self.planner.lib.ms_hades_coin_pow_grind, bits, max_nonce, ctypes.byref(out))
-        return out.value
+        self._create(planner, (ctypes.c_uint64 * 4)(*[(value >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)]))      # canonical words: the library converts
 
     def state(self):
         """-> {"digest": the digest as a canonical integer, "n_draws": the draws made since the last reseed}.  Blocks."""
         st = _lib.HadesCoinState()
-        self._call(self.planner.lib.ms_hades_coin_read, ctypes.byref(st))
+        self._call("read", ctypes.byref(st))
         return {"digest": f252_from_mont_limbs(st.digest), "n_draws": int(st.n_draws)}
 
     def set_state(self, digest, n_draws):
@@ -280,15 +196,4 @@ class PoseidonCoin:
         for k, v in enumerate(f252_to_mont_limbs(int(digest) % F252_P)):
             st.digest[k] = int(v)
         st.n_draws = n_draws
-        self._call(self.planner.lib.ms_hades_coin_write, ctypes.byref(st))
-
-    def close(self):
-        if self.ptr and self.planner.handle:
-            self.planner.lib.ms_hades_coin_destroy(self.planner.handle, self.ptr)
-        self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("write", ctypes.byref(st))

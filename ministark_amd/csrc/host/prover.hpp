@@ -435,104 +435,86 @@ inline uint64_t grind_proof_of_work(Planner& pl, const std::array<uint8_t, 32>& 
     return nonce;
 }
 
-// PublicCoinImpl<F, H> (src/random.rs:61-141) with its state in device memory (ms_coin_*): H = SHA-256, or BLAKE2s-256 / Keccak-256 /
-// SHA3-256 for Hash::Blake2s / Keccak256 / Sha3_256 (ids 0, 1, 3, 4; an RPO-256 prover's coin is SHA-256 unless it asks for RpoCoin, below; id 2 stays unknown).
-// The reseeds and draw() enqueue and return; draw_queries, grind and state wait for the device.
-class PublicCoin {
+// What the three device-resident coins below share: every method is one entry point of the family's table on the coin's handle.  The reseeds
+// and draw() enqueue and return; draw_queries, grind and state wait for the device.  state(): the family's ms_*_coin_state, as stored.
+struct CoinAbi {
+    int (*destroy)(ms_ctx*, void*);
+    int (*read)(ms_ctx*, const void*, void*);
+    int (*reseed_digest)(ms_ctx*, void*, const void*);
+    int (*reseed_int)(ms_ctx*, void*, uint64_t);
+    int (*reseed_elements)(ms_ctx*, void*, int, const void*, size_t);
+    int (*reseed_elements_host)(ms_ctx*, void*, int, const void*, size_t);
+    int (*draw)(ms_ctx*, void*, int, size_t, void*);
+    int (*draw_queries)(ms_ctx*, void*, size_t, size_t, uint64_t*, size_t*);
+    int (*pow_grind)(ms_ctx*, void*, unsigned, uint64_t, uint64_t*);
+};
+template <class State>
+class Coin {
 public:
-    PublicCoin(Planner& pl, const std::array<uint8_t, 32>& seed, Hash h = Hash::Sha256) : pl_(&pl) {                // PublicCoin::new
-        const int id = h == Hash::Blake2s ? MS_HASH_BLAKE2S : h == Hash::Keccak256 ? MS_HASH_KECCAK256 : h == Hash::Sha3_256 ? MS_HASH_SHA3_256 : MS_HASH_SHA256;
-        check(ms_coin_create(pl.ctx(), id, seed.data(), &coin_));
-    }
-    ~PublicCoin() { if (coin_) ms_coin_destroy(pl_->ctx(), coin_); }
-    PublicCoin(const PublicCoin&) = delete; PublicCoin& operator=(const PublicCoin&) = delete;
-    void reseed_digest(const void* d_digest32) { check(ms_coin_reseed_digest(pl_->ctx(), coin_, d_digest32)); }  // e.g. tree.root_ptr()
-    void reseed_int(uint64_t value) { check(ms_coin_reseed_int(pl_->ctx(), coin_, value)); }
-    template <class F> void reseed_elements(const GpuVec<F>& elems, size_t count) { check(ms_coin_reseed_elements(pl_->ctx(), coin_, F::id, elems.ptr(), count)); }
+    ~Coin() { if (coin_) abi_.destroy(pl_->ctx(), coin_); }
+    Coin(const Coin&) = delete; Coin& operator=(const Coin&) = delete;
+    void reseed_digest(const void* d_digest) { check(abi_.reseed_digest(pl_->ctx(), coin_, d_digest)); }          // e.g. tree.root_ptr() of a tree of the coin's hash
+    void reseed_int(uint64_t value) { check(abi_.reseed_int(pl_->ctx(), coin_, value)); }
+    template <class F> void reseed_elements(const GpuVec<F>& elems, size_t count) { check(abi_.reseed_elements(pl_->ctx(), coin_, F::id, elems.ptr(), count)); }
     template <class F> void reseed_elements(const GpuVec<F>& elems) { reseed_elements(elems, elems.len()); }
     template <class F> void reseed_elements(const std::vector<uint64_t>& mont_words) {                            // host elements, Montgomery words
-        check(ms_coin_reseed_elements_host(pl_->ctx(), coin_, F::id, mont_words.data(), mont_words.size() / F::words));
+        check(abi_.reseed_elements_host(pl_->ctx(), coin_, F::id, mont_words.data(), mont_words.size() / F::words));
     }
-    template <class F> GpuVec<F> draw(size_t count = 1) { GpuVec<F> out(*pl_, count); check(ms_coin_draw(pl_->ctx(), coin_, F::id, count, out.ptr())); return out; }
+    template <class F> GpuVec<F> draw(size_t count = 1) { GpuVec<F> out(*pl_, count); check(abi_.draw(pl_->ctx(), coin_, F::id, count, out.ptr())); return out; }
     std::vector<size_t> draw_queries(size_t max_n, size_t domain_size) {
         std::vector<uint64_t> pos(max_n ? max_n : 1);
         size_t n = 0;
-        check(ms_coin_draw_queries(pl_->ctx(), coin_, max_n, domain_size, pos.data(), &n));
+        check(abi_.draw_queries(pl_->ctx(), coin_, max_n, domain_size, pos.data(), &n));
         return std::vector<size_t>(pos.begin(), pos.begin() + n);
     }
-    uint64_t grind(unsigned bits, uint64_t max_nonce = (uint64_t)1 << 40) { uint64_t nonce = 0; check(ms_coin_pow_grind(pl_->ctx(), coin_, bits, max_nonce, &nonce)); return nonce; }
-    ms_coin_state state() const { ms_coin_state st; check(ms_coin_read(pl_->ctx(), coin_, &st)); return st; }
-private:
+    uint64_t grind(unsigned bits, uint64_t max_nonce = (uint64_t)1 << 40) { uint64_t nonce = 0; check(abi_.pow_grind(pl_->ctx(), coin_, bits, max_nonce, &nonce)); return nonce; }
+    State state() const { State st; check(abi_.read(pl_->ctx(), coin_, &st)); return st; }
+protected:
+    Coin(Planner& pl, const CoinAbi& abi) : pl_(&pl), abi_(abi) {}                                                // the family's constructor creates coin_
     Planner* pl_;
+    const CoinAbi& abi_;
     void* coin_ = nullptr;
+};
+
+// PublicCoinImpl<F, H> (src/random.rs:61-141) with its state in device memory (ms_coin_*): H = SHA-256, or BLAKE2s-256 / Keccak-256 /
+// SHA3-256 for Hash::Blake2s / Keccak256 / Sha3_256 (ids 0, 1, 3, 4; an RPO-256 prover's coin is SHA-256 unless it asks for RpoCoin, below; id 2 stays unknown).
+class PublicCoin : public Coin<ms_coin_state> {
+    static constexpr CoinAbi abi = {ms_coin_destroy, ms_coin_read, ms_coin_reseed_digest, ms_coin_reseed_int, ms_coin_reseed_elements, ms_coin_reseed_elements_host,
+                                    ms_coin_draw, ms_coin_draw_queries, ms_coin_pow_grind};
+public:
+    PublicCoin(Planner& pl, const std::array<uint8_t, 32>& seed, Hash h = Hash::Sha256) : Coin(pl, abi) {          // PublicCoin::new
+        const int id = h == Hash::Blake2s ? MS_HASH_BLAKE2S : h == Hash::Keccak256 ? MS_HASH_KECCAK256 : h == Hash::Sha3_256 ? MS_HASH_SHA3_256 : MS_HASH_SHA256;
+        check(ms_coin_create(pl.ctx(), id, seed.data(), &coin_));
+    }
 };
 
 // The RPO-256 public coin (ms_rpo_coin_*, include/ministark_hip_rpo_coin.h): PublicCoin's methods over a 12-element sponge that absorbs and
 // draws Goldilocks elements (Fp or Fq3), for a prover whose verifier runs inside another proof.  seed: four canonical integers below p.
-// The reseeds and draw() enqueue and return; draw_queries, grind and state wait for the device.  state(): Montgomery words, as stored.
-class RpoCoin {
+// state(): Montgomery words.
+class RpoCoin : public Coin<ms_rpo_coin_state> {
+    static constexpr CoinAbi abi = {ms_rpo_coin_destroy, ms_rpo_coin_read, ms_rpo_coin_reseed_digest, ms_rpo_coin_reseed_int, ms_rpo_coin_reseed_elements,
+                                    ms_rpo_coin_reseed_elements_host, ms_rpo_coin_draw, ms_rpo_coin_draw_queries, ms_rpo_coin_pow_grind};
 public:
-    RpoCoin(Planner& pl, const std::array<uint64_t, 4>& seed) : pl_(&pl) {
+    RpoCoin(Planner& pl, const std::array<uint64_t, 4>& seed) : Coin(pl, abi) {
         uint64_t m[4];
         for (int q = 0; q < 4; q++) { if (seed[q] >= gl::P) throw std::invalid_argument("RpoCoin: seed words are below p"); m[q] = gl::to_mont(seed[q]); }
         check(ms_rpo_coin_create(pl.ctx(), m, &coin_));
     }
-    ~RpoCoin() { if (coin_) ms_rpo_coin_destroy(pl_->ctx(), coin_); }
-    RpoCoin(const RpoCoin&) = delete; RpoCoin& operator=(const RpoCoin&) = delete;
-    void reseed_digest(const void* d_digest4) { check(ms_rpo_coin_reseed_digest(pl_->ctx(), coin_, d_digest4)); }   // e.g. the root_ptr() of an RPO-256 tree
-    void reseed_int(uint64_t value) { check(ms_rpo_coin_reseed_int(pl_->ctx(), coin_, value)); }
-    template <class F> void reseed_elements(const GpuVec<F>& elems, size_t count) { check(ms_rpo_coin_reseed_elements(pl_->ctx(), coin_, F::id, elems.ptr(), count)); }
-    template <class F> void reseed_elements(const GpuVec<F>& elems) { reseed_elements(elems, elems.len()); }
-    template <class F> void reseed_elements(const std::vector<uint64_t>& mont_words) {                            // host elements, Montgomery words
-        check(ms_rpo_coin_reseed_elements_host(pl_->ctx(), coin_, F::id, mont_words.data(), mont_words.size() / F::words));
-    }
-    template <class F> GpuVec<F> draw(size_t count = 1) { GpuVec<F> out(*pl_, count); check(ms_rpo_coin_draw(pl_->ctx(), coin_, F::id, count, out.ptr())); return out; }
-    std::vector<size_t> draw_queries(size_t max_n, size_t domain_size) {
-        std::vector<uint64_t> pos(max_n ? max_n : 1);
-        size_t n = 0;
-        check(ms_rpo_coin_draw_queries(pl_->ctx(), coin_, max_n, domain_size, pos.data(), &n));
-        return std::vector<size_t>(pos.begin(), pos.begin() + n);
-    }
-    uint64_t grind(unsigned bits, uint64_t max_nonce = (uint64_t)1 << 40) { uint64_t nonce = 0; check(ms_rpo_coin_pow_grind(pl_->ctx(), coin_, bits, max_nonce, &nonce)); return nonce; }
-    ms_rpo_coin_state state() const { ms_rpo_coin_state st; check(ms_rpo_coin_read(pl_->ctx(), coin_, &st)); return st; }
-private:
-    Planner* pl_;
-    void* coin_ = nullptr;
 };
 
 // The Poseidon public coin of the 252-bit field (ms_hades_coin_*, include/ministark_hip_hades_coin.h): RpoCoin's methods over one field
 // element and a draw counter, for an Fp252 prover that commits with Hash::Poseidon252 and whose verifier runs inside another proof.
-// seed: one element below p as four canonical little-endian words.  The reseeds and draw() enqueue and return; draw_queries, grind and
-// state wait for the device.  state(): the digest in Montgomery words, as stored.
-class PoseidonCoin {
+// seed: one element below p as four canonical little-endian words.  state(): the digest in Montgomery words.
+class PoseidonCoin : public Coin<ms_hades_coin_state> {
+    static constexpr CoinAbi abi = {ms_hades_coin_destroy, ms_hades_coin_read, ms_hades_coin_reseed_digest, ms_hades_coin_reseed_int, ms_hades_coin_reseed_elements,
+                                    ms_hades_coin_reseed_elements_host, ms_hades_coin_draw, ms_hades_coin_draw_queries, ms_hades_coin_pow_grind};
 public:
-    PoseidonCoin(Planner& pl, const std::array<uint64_t, 4>& seed) : pl_(&pl) {
+    PoseidonCoin(Planner& pl, const std::array<uint64_t, 4>& seed) : Coin(pl, abi) {
         lib252::f252::E e;
         for (int q = 0; q < 4; q++) e.l[q] = seed[q];
         if (lib252::f252::geq_p(e)) throw std::invalid_argument("PoseidonCoin: the seed is below p");
         check(ms_hades_coin_create(pl.ctx(), seed.data(), &coin_));
     }
-    ~PoseidonCoin() { if (coin_) ms_hades_coin_destroy(pl_->ctx(), coin_); }
-    PoseidonCoin(const PoseidonCoin&) = delete; PoseidonCoin& operator=(const PoseidonCoin&) = delete;
-    void reseed_digest(const void* d_digest) { check(ms_hades_coin_reseed_digest(pl_->ctx(), coin_, d_digest)); }   // e.g. the root_ptr() of a Poseidon252 tree
-    void reseed_int(uint64_t value) { check(ms_hades_coin_reseed_int(pl_->ctx(), coin_, value)); }
-    template <class F> void reseed_elements(const GpuVec<F>& elems, size_t count) { check(ms_hades_coin_reseed_elements(pl_->ctx(), coin_, F::id, elems.ptr(), count)); }
-    template <class F> void reseed_elements(const GpuVec<F>& elems) { reseed_elements(elems, elems.len()); }
-    template <class F> void reseed_elements(const std::vector<uint64_t>& mont_words) {                            // host elements, Montgomery words
-        check(ms_hades_coin_reseed_elements_host(pl_->ctx(), coin_, F::id, mont_words.data(), mont_words.size() / F::words));
-    }
-    template <class F> GpuVec<F> draw(size_t count = 1) { GpuVec<F> out(*pl_, count); check(ms_hades_coin_draw(pl_->ctx(), coin_, F::id, count, out.ptr())); return out; }
-    std::vector<size_t> draw_queries(size_t max_n, size_t domain_size) {
-        std::vector<uint64_t> pos(max_n ? max_n : 1);
-        size_t n = 0;
-        check(ms_hades_coin_draw_queries(pl_->ctx(), coin_, max_n, domain_size, pos.data(), &n));
-        return std::vector<size_t>(pos.begin(), pos.begin() + n);
-    }
-    uint64_t grind(unsigned bits, uint64_t max_nonce = (uint64_t)1 << 40) { uint64_t nonce = 0; check(ms_hades_coin_pow_grind(pl_->ctx(), coin_, bits, max_nonce, &nonce)); return nonce; }
-    ms_hades_coin_state state() const { ms_hades_coin_state st; check(ms_hades_coin_read(pl_->ctx(), coin_, &st)); return st; }
-private:
-    Planner* pl_;
-    void* coin_ = nullptr;
 };
 
 // DeepPolyComposer::new(air, z, base_trace_polys, extension_trace_polys, composition_trace_polys)

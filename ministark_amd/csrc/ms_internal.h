@@ -69,10 +69,10 @@ struct ms_ctx {
     std::multimap<size_t, void*> pool;
     size_t pool_bytes = 0, pool_cap = (size_t)96 << 30;
     std::map<void*, size_t> live;            // size of every block handed out by ms_alloc
-    std::map<void*, int> coins;              // public coins created on this context (ms_coin.cpp): device state -> MS_HASH_*
-    std::map<void*, int> rpo_coins;          // RPO-256 coins (ms_rpo_coin.cpp): a registry of its own, so that neither family takes the other's handles
-    std::map<void*, uint64_t> hades_coins;   // Poseidon coins of the 252-bit field (ms_hades_coin.cpp), again a registry of its own; the value mirrors the
-                                             // record's n_draws (every change of it is a call of this library), so a draw past 2^64 is refused without a host wait
+    // The public coins created on this context, all three families in one registry keyed by the device state (coin_host.h).  `family` keeps one family's entry points from
+    // taking another's handles, `hash` is the byte coin's MS_HASH_*, n_draws mirrors a Poseidon coin's counter (ms_hades_coin.cpp): a draw past 2^64 is refused without a host wait.
+    struct CoinRec { int family, hash; uint64_t n_draws; };
+    std::map<void*, CoinRec> coins;
     // pinned staging ring for the small host arrays entry points take (query positions, digest indices): the copy to the
     // device is then truly asynchronous and the call does not drain the stream (stage_upload)
     char* stage = nullptr;
