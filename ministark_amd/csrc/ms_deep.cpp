@@ -95,9 +95,8 @@ static int deep_compose252(ms_ctx* ctx, unsigned log_n, const void* h_offset, co
         if (h_term_col[t] >= ncols || h_term_point[t] >= npoints) return fail(MS_ERR_INVALID, "term %u out of range", t);
     MSCHK(deep_canon(ctx, "ms_deep_compose", MS_STARK252_FP, h_offset, (size_t)1 << log_n, d_polys, "d_base_polys", ncols, nullptr, "d_ext_polys", 0, h_points, npoints,
                      h_term_alpha, h_term_ood, nterms, h_degree_alpha, h_degree_beta));
-    f252::E h = f252::to_mont(f252::E{{3, 0, 0, 0}});          // the field's generator (gpu/src/fields.rs:241)
-    if (h_offset) memcpy(h.l, h_offset, 32);
-    if (f252::is_zero(h) || f252::geq_p(h)) return fail(MS_ERR_INVALID, "coset offset must be a non-zero canonical element");
+    f252::E h;
+    MSCHK(offset252(h_offset, &h, f252::to_mont(f252::E{{3, 0, 0, 0}})));          // default: the field's generator (gpu/src/fields.rs:241)
     const size_t n = (size_t)1 << log_n;
     {   // a point ON the evaluation coset has no quotient there: (z / h)^n = 1 (as ms_deep_compose over Goldilocks and deep_rows252 refuse it)
         const f252::E hinv = f252::inv(h);
@@ -171,9 +170,8 @@ static int deep_rows252(ms_ctx* ctx, unsigned log_domain, const void* h_offset, 
         if (h_term_col[t] >= ncols || h_term_point[t] >= npoints) return fail(MS_ERR_INVALID, "term %u out of range", t);
     MSCHK(deep_canon(ctx, "ms_deep_rows", MS_STARK252_FP, h_offset, count, d_rows, "d_base_rows", ncols, nullptr, "d_ext_rows", 0, h_points, npoints,
                      h_term_alpha, h_term_ood, nterms, h_degree_alpha, h_degree_beta));
-    f252::E h = f252::to_mont(f252::E{{3, 0, 0, 0}});          // the field's generator, as deep_compose252
-    if (h_offset) memcpy(h.l, h_offset, 32);
-    if (f252::is_zero(h) || f252::geq_p(h)) return fail(MS_ERR_INVALID, "coset offset must be a non-zero canonical element");
+    f252::E h;
+    MSCHK(offset252(h_offset, &h, f252::to_mont(f252::E{{3, 0, 0, 0}})));          // default: the field's generator, as deep_compose252
     const f252::E hinv = f252::inv(h);
     for (unsigned k = 0; k < npoints; k++) {                   // a point ON the LDE coset has no quotient there: (z / h)^N = 1
         f252::E z;
@@ -372,9 +370,8 @@ extern "C" int ms_deep_compose(ms_ctx* ctx, int point_field, unsigned log_n, con
         if (h_term_col[t] >= nbase + next || h_term_point[t] >= npoints) return fail(MS_ERR_INVALID, "term %u out of range", t);
     MSCHK(deep_canon(ctx, "ms_deep_compose", point_field, h_offset, (size_t)1 << log_n, d_base_polys, "d_base_polys", nbase, d_ext_polys, "d_ext_polys", next,
                      h_points, npoints, h_term_alpha, h_term_ood, nterms, h_degree_alpha, h_degree_beta));
-    uint64_t h = gl::GENERATOR;
-    if (h_offset) { uint64_t h_m; memcpy(&h_m, h_offset, 8); h = gl::from_mont(h_m); }
-    if (h == 0) return fail(MS_ERR_INVALID, "coset offset must be non-zero");
+    uint64_t h;
+    MSCHK(offset_gl(h_offset, &h, gl::GENERATOR));
     const size_t n = (size_t)1 << log_n;
     // Q is evaluated on the coset h<w_n> and a lane shares ONE inversion between the denominators x - z_k of its points: a point
     // z_k ON that coset (possible only when it lies in the base field: probability about n / p per drawn point) has no quotient
@@ -507,9 +504,8 @@ extern "C" int ms_deep_rows(ms_ctx* ctx, int point_field, unsigned log_domain, c
         if (h_term_col[t] >= nbase + next || h_term_point[t] >= npoints) return fail(MS_ERR_INVALID, "term %u out of range", t);
     MSCHK(deep_canon(ctx, "ms_deep_rows", point_field, h_offset, count, d_base_rows, "d_base_rows", nbase, d_ext_rows, "d_ext_rows", next,
                      h_points, npoints, h_term_alpha, h_term_ood, nterms, h_degree_alpha, h_degree_beta));
-    uint64_t h = gl::GENERATOR;
-    if (h_offset) { uint64_t h_m; memcpy(&h_m, h_offset, 8); h = gl::from_mont(h_m); }
-    if (h == 0) return fail(MS_ERR_INVALID, "coset offset must be non-zero");
+    uint64_t h;
+    MSCHK(offset_gl(h_offset, &h, gl::GENERATOR));
     for (unsigned k = 0; k < npoints; k++) {           // a point ON the LDE coset has no quotient there (cf. ms_deep_compose)
         const uint64_t* zk = (const uint64_t*)h_points + (size_t)k * PW;
         if (PW == 3 && (zk[1] != 0 || zk[2] != 0)) continue;

@@ -1,7 +1,7 @@
-// Internal declarations shared by the translation units of libministark_hip.so (ms_core / ms_ntt / ms_stage / ms_hash / ms_eval / ms_deep /
+// Internal declarations shared by the translation units of libministark_hip.so (ms_core / ms_ntt_plan / ms_ntt / ms_ntt252 / ms_stage / ms_hash / ms_eval / ms_deep /
 // ms_comm / ms_validate / ms_blake2s / ms_canon / ms_coin / ms_keccak / ms_ext / ms_logup / ms_rpo_coin / ms_lookup / ms_sort / ms_gaps / ms_join / ms_poseidon .cpp,
-// the SOURCES of build.py): the context, the plan object, error plumbing, pooled scratch, the checked mode's scans and the base-column
-// arguments of the trace-table entry points.  Not part of the C ABI.
+// the SOURCES of build.py): the context, the plan object and what the three NTT units share, error plumbing, the coset-offset decoders, pooled
+// scratch, the checked mode's scans and the base-column arguments of the trace-table entry points.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,6 +43,20 @@ static inline bool ranges_overlap(const void* a, size_t na, const void* b, size_
     return p < q + nb && q < p + na;
 }
 
+// The coset offset an entry point takes, one decoder per field: a null pointer is `dflt`, zero is refused ("<what> offset must be ...").
+// Goldilocks: the Montgomery word in, the canonical residue out.  252-bit field: Montgomery limbs in and out, refused unless canonical too.
+static inline int offset_gl(const void* h_offset, uint64_t* h, uint64_t dflt = 1, const char* what = "coset") {
+    *h = dflt;
+    if (h_offset) { uint64_t h_m; memcpy(&h_m, h_offset, 8); *h = gl::from_mont(h_m); }
+    if (*h == 0) return fail(MS_ERR_INVALID, "%s offset must be non-zero", what);
+    return MS_OK;
+}
+static inline int offset252(const void* h_offset, f252::E* h, const f252::E& dflt = f252::one(), const char* what = "coset") {
+    *h = dflt;
+    if (h_offset) memcpy(h->l, h_offset, 32);
+    if (f252::is_zero(*h) || f252::geq_p(*h)) return fail(MS_ERR_INVALID, "%s offset must be a non-zero canonical element", what);
+    return MS_OK;
+}
 
 // what the specialised constraint kernels cost and where they came from (eval_jit.h, jit_cache.h; ms_eval_jit_stats)
 struct JitStats { uint64_t compiled = 0, from_disk = 0, failures = 0, damaged_entries = 0; double compile_ms = 0, load_ms = 0; };
@@ -222,11 +236,21 @@ struct BaseColumns {
     int mask(int kind, int mask_col, const char* who, const uint64_t** ptr);   // "<who>unknown mask kind %d", "<who>mask column %d out of range (%u)"
 };
 
-// ms_ntt.cpp
+// ms_ntt_plan.cpp: plans and their tables (host only).  ctx_plan / plan252_cached / plan_oscale / lde2_tables: the caller holds ctx->mu.
+// (MS_LOCAL: what the split of ms_ntt.cpp made cross-unit stays out of the library's dynamic symbol table, which is as it was.)
+#define MS_LOCAL __attribute__((visibility("hidden")))
 int ctx_plan(ms_ctx* ctx, unsigned V, unsigned log_n, bool inverse, uint64_t h, ms_ntt_plan** out);     // the context's cached plan
-int plan252_cached(ms_ctx* ctx, unsigned log_n, bool inverse, const f252::E& h, ms_ntt_plan** out);
-int plan_run(ms_ntt_plan* p, const void* const* src, void* const* dst, unsigned ncols, unsigned valid_rows, bool bitrev_out = false);
-int bit_reverse_run(ms_ctx* ctx, unsigned V, unsigned log_n, const void* const* src, void* const* dst, unsigned ncols);
-unsigned stream_grid(size_t n);
+int plan252_cached(ms_ctx* ctx, unsigned log_n, bool inverse, const f252::E& h, ms_ntt_plan** out);    // h: as offset252 returns it
+MS_LOCAL bool user_plan_alive(ms_ntt_plan* p);                // a plan of ms_ntt_plan_create whose context still exists
 void plans_release_ctx(ms_ctx* ctx);                 // ms_ctx_destroy: plans still held by the caller go with their context
 int plan_free_cached(ms_ntt_plan* plan);             // the context's own (cached) plans
+MS_LOCAL int plan_oscale(ms_ntt_plan* owner);                 // d_oscale of a cached inverse coset plan of 2^18 points, built at first use
+MS_LOCAL int lde2_tables(ms_ntt_plan* fwd, unsigned log_n, unsigned log_b, ms_ntt_plan::Lde2** out);   // of the cached forward plan, per blow-up
+constexpr unsigned NTT252_TILE_LOG = 11;             // = ms252::TILE_LOG (ms_ntt252.cpp asserts it): plans from this size on carry tiled passes
+// ms_ntt252.cpp: the 252-bit field's transforms
+MS_LOCAL int plan_run252(ms_ntt_plan* p, const void* const* src, void* const* dst, unsigned ncols);
+MS_LOCAL int plan_run252_tiled(ms_ntt_plan* p, const void* const* src, void* const* dst, unsigned ncols, unsigned log_zero_ext, bool bitrev_out);
+// ms_ntt.cpp: the Goldilocks routes (plan_run hands a 252-bit plan on), bit reversal
+int plan_run(ms_ntt_plan* p, const void* const* src, void* const* dst, unsigned ncols, unsigned valid_rows, bool bitrev_out = false);
+int bit_reverse_run(ms_ctx* ctx, unsigned V, unsigned log_n, const void* const* src, void* const* dst, unsigned ncols);
+unsigned stream_grid(size_t n);                      // ms_stage.cpp: the grid of a grid-stride kernel over n elements

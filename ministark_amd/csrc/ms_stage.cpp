@@ -281,9 +281,8 @@ static int fri_fold_impl(ms_ctx* ctx, const char* entry, int field, unsigned log
         MSCHK(canon_col(ctx, entry, "d_evals", field, nchunks * folding_factor, d_evals));
     }
     if (V == 4) {
-        f252::E h252 = f252::one();
-        if (h_offset) memcpy(h252.l, h_offset, 32);
-        if (f252::is_zero(h252) || f252::geq_p(h252)) return fail(MS_ERR_INVALID, "domain offset must be a non-zero canonical element");
+        f252::E h252;
+        MSCHK(offset252(h_offset, &h252, f252::one(), "domain"));
         std::lock_guard<std::mutex> lk(ctx->mu);
         HIPCHK(hipSetDevice(ctx->device));
         ms_ntt_plan* plan = nullptr;
@@ -318,9 +317,8 @@ static int fri_fold_impl(ms_ctx* ctx, const char* entry, int field, unsigned log
         HIPCHK(hipGetLastError());
         return MS_OK;
     }
-    uint64_t h = 1;
-    if (h_offset) { uint64_t h_m; memcpy(&h_m, h_offset, 8); h = gl::from_mont(h_m); }
-    if (h == 0) return fail(MS_ERR_INVALID, "domain offset must be non-zero");
+    uint64_t h;
+    MSCHK(offset_gl(h_offset, &h, 1, "domain"));
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
     // powers of w_n^-1: the tables of the size-n inverse plan (multi-pass layout needs log_n >= 12;

@@ -29,7 +29,7 @@ this table with the hipLaunchKernelGGL lines of ms_deep.cpp and with the cases b
 
 Sizes trimmed under the simulator (kinds of case are not): ms_horner_eval at n around 4096^2 runs one of its three lengths there
 (4096^2 + 1, the three-level one); the 252-bit domain of 2^22 points (the smallest whose two-level twiddle table has an upper level:
-lo_bits = min(21, log_n) in ms_ntt.cpp) runs on the device only.
+lo_bits = min(21, log_n) in ms_ntt_plan.cpp) runs on the device only.
 
 Rules pinned here and stated in include/ministark_hip.h: log_n = 0 and 1 of ms_deep_compose give the reference's words; nterms = 0 gives
 an all-zero output; d_out overlapping an input column is refused (MS_ERR_INVALID, "overlap") before anything is enqueued."""
@@ -120,7 +120,7 @@ def _rows_cases():
             out.append(Rows(f, 12, 3, 300, 5, 1, "rand", ("base", "x"), "nbase0", both))
             out.append(Rows(f, 13, 3, 4099, 4, None, "rand", ("base", "x"), "next0", both))
         if f == F252:
-            # lo_bits = min(21, log_n) for the 252-bit tables (ms_ntt.cpp): 2^22 points is the smallest domain with an upper level, and
+            # lo_bits = min(21, log_n) for the 252-bit tables (ms_ntt_plan.cpp): 2^22 points is the smallest domain with an upper level, and
             # bitrev(first + i) >= 2^21 at every odd position
             out.append(Rows(f, 22, (1 << 21) + 12345, 1025, 3, None, "rand", (), None, ("hip",)))
     return out

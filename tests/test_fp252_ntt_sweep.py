@@ -1,10 +1,10 @@
 """Sweep of the 252-bit transforms through the C ABI: ms_ntt_enqueue / ms_ntt_enqueue_to, ms_lde and ms_evaluate on Fp252 columns, at the sizes,
-values, batch widths and blow-ups where csrc/ms_ntt.cpp changes route and where the lazily reduced tiles of csrc/fp252_ntt_kernels.h could
+values, batch widths and blow-ups where csrc/ms_ntt252.cpp and csrc/ms_ntt.cpp change route and where the lazily reduced tiles of csrc/fp252_ntt_kernels.h could
 come out wrong.  Every output word is compared with the C oracle (oracle.cref.ntt252 / lde252 / bit_reverse, pinned to the big-integer
 restatement by tests/test_fp252_parity.py::test_c_oracle_ntt_252_matches_bigint), bit for bit; the zero and the constant columns also with
 their closed forms, which need no oracle.
 
-The routes (ms_ntt.cpp).  Below 2^11 points a column is bit-reversed, transformed by ntt252_local (up to 2^9 points in LDS) and, above 2^9,
+The routes (plan_run252 in ms_ntt252.cpp, the plans of plan_build252 in ms_ntt_plan.cpp, ms_lde / ms_evaluate in ms_ntt.cpp).  Below 2^11 points a column is bit-reversed, transformed by ntt252_local (up to 2^9 points in LDS) and, above 2^9,
 by ntt252_stages, one column per launch, through a device copy when the transform is out of place (plan_run252).  From 2^11 points on the tiled
 passes run (plan_run252_tiled): two passes up to 2^20 points, three above (MS_NTT252_PASSES=3: from 2^17 on), with the radices
 lr252 = log_n split evenly, the larger ones first -- (6, 5) at 2^11, (6, 6) at 2^12, (7, 6) at 2^13, (6, 6, 5) at a three-pass 2^17, (9, 9) at
