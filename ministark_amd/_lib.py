@@ -207,6 +207,13 @@ class Lib:
             "ms_keccak_merkle": (i, [vp, i, sz, vp, vp]),
             "ms_keccak_pow_grind": (i, [vp, i, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
         }
+        # include/ministark_hip_blake3.h: BLAKE3 commitments and proof-of-work, each the twin of its ms_blake2s_* namesake
+        blake3_sigs = {
+            "ms_blake3_rows": (i, [vp, i, sz, c_void_pp, u, vp]),
+            "ms_blake3_rows_row_major": (i, [vp, i, sz, u, vp, vp]),
+            "ms_blake3_merkle": (i, [vp, sz, vp, vp]),
+            "ms_blake3_pow_grind": (i, [vp, vp, u, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        }
         # include/ministark_hip_ext.h: the extension columns between the two trace commitments
         ext_sigs = {
             "ms_build_extension_columns": (i, [vp, i, i, sz, c_void_pp, u, vp, u, vp, vp, u, c_void_pp]),
@@ -261,7 +268,7 @@ class Lib:
         self.optional = {}
         for name, (res, args) in (list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items())
                                   + list(logup_sigs.items()) + list(rpo_coin_sigs.items()) + list(lookup_sigs.items()) + list(sort_sigs.items()) + list(gap_sigs.items())
-                                  + list(join_sigs.items()) + list(poseidon_sigs.items()) + list(hades_coin_sigs.items())):
+                                  + list(join_sigs.items()) + list(poseidon_sigs.items()) + list(hades_coin_sigs.items()) + list(blake3_sigs.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -277,6 +284,7 @@ class Lib:
         self.join_sigs = join_sigs
         self.poseidon_sigs = poseidon_sigs
         self.hades_coin_sigs = hades_coin_sigs
+        self.blake3_sigs = blake3_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

@@ -286,10 +286,10 @@ def _gather_digests(planner, digests, ndigests, ids):
     return _gather_digests_launch(planner, digests, ndigests, ids)()
 
 
-HASHES = ("sha256", "rpo256", "blake2s", "keccak256", "sha3_256", "poseidon252")
+HASHES = ("sha256", "rpo256", "blake2s", "keccak256", "sha3_256", "poseidon252", "blake3_256")
 KECCAK_VARIANTS = {"keccak256": 0, "sha3_256": 1}          # MS_KECCAK256 / MS_SHA3_256 of include/ministark_hip_keccak.h
 # the byte hashes share one set of entry points, ms_<prefix>_{rows, rows_row_major, merkle, pow_grind}: name -> (prefix, leading arguments)
-_BYTE_HASHES = {"sha256": ("sha256", ()), "blake2s": ("blake2s", ()),
+_BYTE_HASHES = {"sha256": ("sha256", ()), "blake2s": ("blake2s", ()), "blake3_256": ("blake3", ()),
                 **{name: ("keccak", (variant,)) for name, variant in KECCAK_VARIANTS.items()}}
 
 
@@ -374,6 +374,9 @@ class MerkleTree:
                 compression instead of two.  Any of the three fields;
       "keccak256" / "sha3_256"  the Keccak sponge with domain byte 0x01 (sha3::Keccak256, the EVM's KECCAK256) / 0x06
                 (hashlib.sha3_256): the same leaf bytes, a merge is one permutation.  Any of the three fields;
+      "blake3_256"  unkeyed BLAKE3 with a 32-byte digest (blake3::hash, Winterfell's Blake3_256): the same leaf bytes -- a row longer
+                than 1024 bytes is BLAKE3's tree of chunks -- and a merge is the plain hash of 64 bytes, one compression of 7 rounds.
+                Any of the three fields;
       "poseidon252"  Starknet's Poseidon (the Hades permutation, t = 3) over STARK252_FP, the algebraic commitment of that field as
                 RPO-256 is Goldilocks': a leaf is hash_many(row), a node hash2(left, right), a digest ONE field element in
                 Montgomery form = 32 bytes (`poseidon252_value` gives its integer).  STARK252_FP matrices and layers only."""
@@ -772,7 +775,7 @@ class Matrix:
     def hash_rows(self, hash="sha256"):
         """`hash_rows::<F, H>` (src/merkle.rs:412-436, src/matrix.rs:254-280): one digest per row ->
         DeviceBytes of num_rows x 32.  H = Sha256HashFn ("sha256"), RPO-256 ("rpo256", Goldilocks columns), BLAKE2s-256 ("blake2s"),
-        Keccak-256 ("keccak256"), SHA3-256 ("sha3_256") or Starknet's Poseidon ("poseidon252", STARK252_FP columns: a digest is one element)."""
+        Keccak-256 ("keccak256"), SHA3-256 ("sha3_256"), BLAKE3 ("blake3_256") or Starknet's Poseidon ("poseidon252", STARK252_FP columns: a digest is one element)."""
         pl = self.planner
         n = self.num_rows()
         if hash == "poseidon252" and self.field != STARK252_FP:
@@ -956,19 +959,19 @@ def poseidon252_value(digest_bytes):
 
 
 def pow_hash(commitment_hash):
-    """The proof-of-work hash of a prover that commits with `commitment_hash`: BLAKE2s grinds with BLAKE2s, Keccak-256 and SHA3-256
-    with themselves; SHA-256, RPO-256 and Poseidon provers grind with SHA-256, as they always have."""
-    return commitment_hash if commitment_hash in ("blake2s", "keccak256", "sha3_256") else "sha256"
+    """The proof-of-work hash of a prover that commits with `commitment_hash`: BLAKE2s grinds with BLAKE2s, Keccak-256, SHA3-256
+    and BLAKE3 with themselves; SHA-256, RPO-256 and Poseidon provers grind with SHA-256, as they always have."""
+    return commitment_hash if commitment_hash in ("blake2s", "keccak256", "sha3_256", "blake3_256") else "sha256"
 
 
 def grind_proof_of_work(planner, seed, proof_of_work_bits, max_nonce=(1 << 40), hash="sha256"):
     """`PublicCoin::grind_proof_of_work(bits)` (src/random.rs:48-55): the smallest nonce >= 1 whose
     H(seed || nonce_be) has `bits` leading zero bits.  seed: 32 bytes.  H = SHA-256 ("sha256"), BLAKE2s-256 ("blake2s"),
-    Keccak-256 ("keccak256") or SHA3-256 ("sha3_256")."""
+    Keccak-256 ("keccak256"), SHA3-256 ("sha3_256") or BLAKE3 ("blake3_256")."""
     seed = bytes(seed)
     assert len(seed) == 32
     if hash not in _BYTE_HASHES:
-        raise ValueError(f"unknown proof-of-work hash {hash!r} (sha256, blake2s, keccak256 or sha3_256)")
+        raise ValueError(f"unknown proof-of-work hash {hash!r} (sha256, blake2s, keccak256, sha3_256 or blake3_256)")
     out = ctypes.c_uint64(0)
     buf = ctypes.create_string_buffer(seed, 32)
     _byte_hash_call(planner, hash, "pow_grind", buf, proof_of_work_bits, max_nonce, ctypes.byref(out))

@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib
 from .api import F252_P, FIELD_WORDS, GL_P, DeviceBytes, GpuVec, f252_from_mont_limbs, f252_to_mont_limbs, gl_from_mont, gl_to_mont
 
-HASH_IDS = {"sha256": 0, "blake2s": 1, "keccak256": 3, "sha3_256": 4}        # 2 stays unknown: the RPO-256 coin is RpoCoin, a family of its own
+HASH_IDS = {"sha256": 0, "blake2s": 1, "keccak256": 3, "sha3_256": 4, "blake3_256": 6}        # 2 and 5 stay unknown: the RPO-256 coin is RpoCoin, a family of its own
 
 
 class _Coin:
@@ -83,7 +83,7 @@ class _Coin:
 
 
 class PublicCoin(_Coin):
-    """`PublicCoin::new(seed)` (src/random.rs:102-109).  seed32: 32 bytes; hash: "sha256" (Sha256HashFn), "blake2s", "keccak256" or "sha3_256"."""
+    """`PublicCoin::new(seed)` (src/random.rs:102-109).  seed32: 32 bytes; hash: "sha256" (Sha256HashFn), "blake2s", "keccak256", "sha3_256" or "blake3_256"."""
 
     _prefix = "ms_coin_"
 

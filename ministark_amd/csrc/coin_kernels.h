@@ -1,6 +1,6 @@
 // The public coin of the Fiat-Shamir transcript, resident on the device: PublicCoinImpl<F, H> (src/random.rs:61-141) as
-// ProverChannel drives it (src/channel.rs:46-100, src/fri.rs:217-247), for H = SHA-256, BLAKE2s-256, Keccak-256 and SHA3-256
-// (the template parameter H is ms_coin_create's hash id: 0, 1, 3, 4; 2 stays unknown -- the RPO-256 coin is a sponge, not a seed and a counter, and has a family of its own: rpo_coin_kernels.h, ms_rpo_coin_*).
+// ProverChannel drives it (src/channel.rs:46-100, src/fri.rs:217-247), for H = SHA-256, BLAKE2s-256, Keccak-256, SHA3-256 and BLAKE3
+// (the template parameter H is ms_coin_create's hash id: 0, 1, 3, 4, 6; 5 stays unknown, and so does 2 -- the RPO-256 coin is a sponge, not a seed and a counter, and has a family of its own: rpo_coin_kernels.h, ms_rpo_coin_*).
 //
 // State (ms_coin_state of include/ministark_hip_transcript.h, 80 bytes in HBM): a 32-byte seed, a u64 counter and up to 32 unread bytes of the
 // last digest.  The rules, one device function each:
@@ -17,7 +17,7 @@
 // These are dependent chains of a few compressions: latency-bound, no roofline.  Every kernel is ONE wave; lane 0 walks the chain
 // (the state lives in its registers between the load and the store), and in coin_reseed_elements all 64 lanes hash the per-element
 // digests of a batch in parallel before lane 0 merges them in order.  The compression functions are those of sha256_kernels.h /
-// blake2s_kernels.h / keccak_sponge.h (every message here is one Keccak block; the chains keep the permutation as a short loop).  Only the proof-of-work search (one nonce per lane, as sha256_pow_grind) is a wide launch.
+// blake2s_kernels.h / keccak_sponge.h / blake3_kernels.h (every message here is one Keccak block and one BLAKE3 block; the chains keep the permutation as a short loop).  Only the proof-of-work search (one nonce per lane, as sha256_pow_grind) is a wide launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "gl.h"
@@ -26,6 +26,7 @@
 #include "sha256_kernels.h"
 #include "blake2s_kernels.h"
 #include "keccak_sponge.h"
+#include "blake3_kernels.h"
 
 namespace mscoin {
 
@@ -66,8 +67,16 @@ __device__ __forceinline__ void hash_short(const uint32_t (&m)[16], unsigned len
         s.load_short(m, len / 8, H == 3 ? mskec::DOMAIN_KECCAK : mskec::DOMAIN_SHA3);
         s.permute<mskec::UNROLL_CHAIN>();
         s.digest(out);
+    } else if constexpr (H == 6) {               // BLAKE3: one block that is the whole input, block_len = len
+        msb3::B3 s;
+        s.init();
+        #pragma unroll
+        for (int q = 0; q < 16; q++) s.m[q] = m[q];
+        s.compress(0, len, msb3::ONE_BLOCK);
+        #pragma unroll
+        for (int q = 0; q < 8; q++) out[q] = s.cv[q];
     } else {                                     // BLAKE2s: one final block, counter = len
-        static_assert(H == 1, "hash ids: 0 SHA-256, 1 BLAKE2s-256, 3 Keccak-256, 4 SHA3-256");
+        static_assert(H == 1, "hash ids: 0 SHA-256, 1 BLAKE2s-256, 3 Keccak-256, 4 SHA3-256, 6 BLAKE3");
         msb2s::B2s s;
         s.init();
         #pragma unroll

@@ -24,6 +24,7 @@
 
 #include "../../../include/ministark_hip.h"
 #include "../../../include/ministark_hip_keccak.h"
+#include "../../../include/ministark_hip_blake3.h"
 #include "../../../include/ministark_hip_poseidon.h"
 
 namespace ms {
@@ -318,10 +319,12 @@ public:
 // H of MatrixMerkleTreeImpl<H> (src/merkle.rs:296-361): Sha256HashFn (src/hash.rs:58-100), RPO-256 over
 // Goldilocks (gpu/src/plan.rs:32-174, README.md:90) or BLAKE2s-256 (any field; the bytes SHA-256 hashes, one compression per
 // merge), or the Keccak sponge as Keccak-256 (the EVM's KECCAK256) / SHA3-256 (any field; the same bytes, one permutation per merge).
+// Blake3_256 is unkeyed BLAKE3 with a 32-byte digest (any field; the same bytes, a row past 1024 bytes as BLAKE3's tree of chunks; a
+// merge is the plain hash of 64 bytes, one compression of 7 rounds).
 // Poseidon252 is Starknet's Poseidon over the 252-bit field (include/ministark_hip_poseidon.h), the algebraic commitment of Fp252 as RPO-256
 // is Goldilocks': a digest is one field element in Montgomery form; matrices and layers of Fp252 only (std::invalid_argument otherwise).
 // All digests are 32 bytes, proofs have the same shape.
-enum class Hash { Sha256, Rpo256, Blake2s, Keccak256, Sha3_256, Poseidon252 };
+enum class Hash { Sha256, Rpo256, Blake2s, Keccak256, Sha3_256, Poseidon252, Blake3_256 };
 inline void poseidon_field(int field) {
     if (field != MS_STARK252_FP) throw std::invalid_argument("Hash::Poseidon252 absorbs elements of the 252-bit field (ms::Fp252)");
 }
@@ -331,6 +334,7 @@ inline int hash_rows(ms_ctx* ctx, Hash h, int field, size_t nrows, const void* c
     switch (h) {
         case Hash::Sha256: return ms_sha256_rows(ctx, field, nrows, d_cols, ncols, d_leaves);
         case Hash::Blake2s: return ms_blake2s_rows(ctx, field, nrows, d_cols, ncols, d_leaves);
+        case Hash::Blake3_256: return ms_blake3_rows(ctx, field, nrows, d_cols, ncols, d_leaves);
         case Hash::Keccak256: case Hash::Sha3_256: return ms_keccak_rows(ctx, keccak_variant(h), field, nrows, d_cols, ncols, d_leaves);
         case Hash::Poseidon252: poseidon_field(field); return ms_poseidon252_rows(ctx, nrows, d_cols, ncols, d_leaves);
         case Hash::Rpo256: break;
@@ -341,6 +345,7 @@ inline int hash_rows_row_major(ms_ctx* ctx, Hash h, int field, size_t nrows, uns
     switch (h) {
         case Hash::Sha256: return ms_sha256_rows_row_major(ctx, field, nrows, ncols, d_matrix, d_leaves);
         case Hash::Blake2s: return ms_blake2s_rows_row_major(ctx, field, nrows, ncols, d_matrix, d_leaves);
+        case Hash::Blake3_256: return ms_blake3_rows_row_major(ctx, field, nrows, ncols, d_matrix, d_leaves);
         case Hash::Keccak256: case Hash::Sha3_256: return ms_keccak_rows_row_major(ctx, keccak_variant(h), field, nrows, ncols, d_matrix, d_leaves);
         case Hash::Poseidon252: poseidon_field(field); return ms_poseidon252_rows_row_major(ctx, nrows, ncols, d_matrix, d_leaves);
         case Hash::Rpo256: break;
@@ -351,6 +356,7 @@ inline int hash_merkle(ms_ctx* ctx, Hash h, size_t nleaves, const void* d_leaves
     switch (h) {
         case Hash::Sha256: return ms_sha256_merkle(ctx, nleaves, d_leaves, d_nodes);
         case Hash::Blake2s: return ms_blake2s_merkle(ctx, nleaves, d_leaves, d_nodes);
+        case Hash::Blake3_256: return ms_blake3_merkle(ctx, nleaves, d_leaves, d_nodes);
         case Hash::Keccak256: case Hash::Sha3_256: return ms_keccak_merkle(ctx, keccak_variant(h), nleaves, d_leaves, d_nodes);
         case Hash::Poseidon252: return ms_poseidon252_merkle(ctx, nleaves, d_leaves, d_nodes);
         case Hash::Rpo256: break;
@@ -361,6 +367,7 @@ inline int hash_merkle(ms_ctx* ctx, Hash h, size_t nleaves, const void* d_leaves
 inline int hash_pow_grind(ms_ctx* ctx, Hash h, const void* h_seed32, unsigned bits, uint64_t max_nonce, uint64_t* nonce) {
     switch (h) {
         case Hash::Blake2s: return ms_blake2s_pow_grind(ctx, h_seed32, bits, max_nonce, nonce);
+        case Hash::Blake3_256: return ms_blake3_pow_grind(ctx, h_seed32, bits, max_nonce, nonce);
         case Hash::Keccak256: case Hash::Sha3_256: return ms_keccak_pow_grind(ctx, keccak_variant(h), h_seed32, bits, max_nonce, nonce);
         case Hash::Sha256: case Hash::Rpo256: case Hash::Poseidon252: break;
     }

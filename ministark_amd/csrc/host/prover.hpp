@@ -427,7 +427,7 @@ private:
 };
 
 // PublicCoin::grind_proof_of_work(bits): the smallest nonce >= 1 with `bits` leading zero bits of H(seed || nonce_be),
-// H = SHA-256 (Hash::Sha256, also what an RPO-256 prover grinds with), BLAKE2s-256 (Hash::Blake2s), Keccak-256 or SHA3-256
+// H = SHA-256 (Hash::Sha256, also what an RPO-256 prover grinds with), BLAKE2s-256 (Hash::Blake2s), Keccak-256, SHA3-256 or BLAKE3 (Hash::Blake3_256)
 inline uint64_t grind_proof_of_work(Planner& pl, const std::array<uint8_t, 32>& seed, unsigned proof_of_work_bits, uint64_t max_nonce = (uint64_t)1 << 40,
                                     Hash h = Hash::Sha256) {
     uint64_t nonce = 0;
@@ -477,13 +477,13 @@ protected:
 };
 
 // PublicCoinImpl<F, H> (src/random.rs:61-141) with its state in device memory (ms_coin_*): H = SHA-256, or BLAKE2s-256 / Keccak-256 /
-// SHA3-256 for Hash::Blake2s / Keccak256 / Sha3_256 (ids 0, 1, 3, 4; an RPO-256 prover's coin is SHA-256 unless it asks for RpoCoin, below; id 2 stays unknown).
+// SHA3-256 / BLAKE3 for Hash::Blake2s / Keccak256 / Sha3_256 / Blake3_256 (ids 0, 1, 3, 4, 6; an RPO-256 prover's coin is SHA-256 unless it asks for RpoCoin, below; ids 2 and 5 stay unknown).
 class PublicCoin : public Coin<ms_coin_state> {
     static constexpr CoinAbi abi = {ms_coin_destroy, ms_coin_read, ms_coin_reseed_digest, ms_coin_reseed_int, ms_coin_reseed_elements, ms_coin_reseed_elements_host,
                                     ms_coin_draw, ms_coin_draw_queries, ms_coin_pow_grind};
 public:
     PublicCoin(Planner& pl, const std::array<uint8_t, 32>& seed, Hash h = Hash::Sha256) : Coin(pl, abi) {          // PublicCoin::new
-        const int id = h == Hash::Blake2s ? MS_HASH_BLAKE2S : h == Hash::Keccak256 ? MS_HASH_KECCAK256 : h == Hash::Sha3_256 ? MS_HASH_SHA3_256 : MS_HASH_SHA256;
+        const int id = h == Hash::Blake2s ? MS_HASH_BLAKE2S : h == Hash::Keccak256 ? MS_HASH_KECCAK256 : h == Hash::Sha3_256 ? MS_HASH_SHA3_256 : h == Hash::Blake3_256 ? MS_HASH_BLAKE3 : MS_HASH_SHA256;
         check(ms_coin_create(pl.ctx(), id, seed.data(), &coin_));
     }
 };

@@ -5,6 +5,7 @@
 // checks and the tails shared with the two algebraic coins: coin_host.h; this file keeps the seed, the rules of ms_coin_write and the launches.
 #include "ms_internal.h"
 #include "../../include/ministark_hip_keccak.h"
+#include "../../include/ministark_hip_blake3.h"
 #include "coin_host.h"
 #include "coin_kernels.h"
 
@@ -12,12 +13,13 @@ using mscoin::State;
 using mscoinhost::BYTE;
 static_assert(sizeof(ms_coin_state) == sizeof(State), "ms_coin_state and its device image must agree");
 
-// f(std::integral_constant<int, H>) with H the kernels' hash index of MS_HASH_*: 0 SHA-256, 1 BLAKE2s, 3 Keccak-256, 4 SHA3-256
+// f(std::integral_constant<int, H>) with H the kernels' hash index of MS_HASH_*: 0 SHA-256, 1 BLAKE2s, 3 Keccak-256, 4 SHA3-256, 6 BLAKE3
 template <class F>
 static void with_hash(int hash, F f) {
     if (hash == MS_HASH_SHA256) f(std::integral_constant<int, 0>());
     else if (hash == MS_HASH_KECCAK256) f(std::integral_constant<int, 3>());
     else if (hash == MS_HASH_SHA3_256) f(std::integral_constant<int, 4>());
+    else if (hash == MS_HASH_BLAKE3) f(std::integral_constant<int, 6>());
     else f(std::integral_constant<int, 1>());
 }
 
@@ -34,7 +36,7 @@ static int any_field(const char*, int field, unsigned* V) { return field_words(f
 
 extern "C" int ms_coin_create(ms_ctx* ctx, int hash, const void* h_seed32, void** d_coin) {
     if (!ctx || !h_seed32 || !d_coin) return fail(MS_ERR_INVALID, "ms_coin_create: null argument");
-    if (hash != MS_HASH_SHA256 && hash != MS_HASH_BLAKE2S && hash != MS_HASH_KECCAK256 && hash != MS_HASH_SHA3_256) return fail(MS_ERR_INVALID, "ms_coin_create: unknown hash id %d", hash);
+    if (hash != MS_HASH_SHA256 && hash != MS_HASH_BLAKE2S && hash != MS_HASH_KECCAK256 && hash != MS_HASH_SHA3_256 && hash != MS_HASH_BLAKE3) return fail(MS_ERR_INVALID, "ms_coin_create: unknown hash id %d", hash);
     State S;
     memset(&S, 0, sizeof S);
     memcpy(S.seed, h_seed32, 32);

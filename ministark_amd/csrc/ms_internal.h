@@ -1,5 +1,5 @@
 // Internal declarations shared by the translation units of libministark_hip.so (ms_core / ms_ntt_plan / ms_ntt / ms_ntt252 / ms_stage / ms_hash / ms_eval / ms_deep /
-// ms_comm / ms_validate / ms_blake2s / ms_canon / ms_coin / ms_keccak / ms_ext / ms_logup / ms_rpo_coin / ms_lookup / ms_sort / ms_gaps / ms_join / ms_poseidon .cpp,
+// ms_comm / ms_validate / ms_blake2s / ms_canon / ms_coin / ms_keccak / ms_ext / ms_logup / ms_rpo_coin / ms_lookup / ms_sort / ms_gaps / ms_join / ms_poseidon / ms_blake3 .cpp,
 // the SOURCES of build.py): the context, the plan object and what the three NTT units share, error plumbing, the coset-offset decoders, pooled
 // scratch, the checked mode's scans and the base-column arguments of the trace-table entry points.  Not part of the C ABI.
 #pragma once

@@ -508,7 +508,7 @@ def _lowered(comp_expr, ncols, field=GOLDILOCKS_FP, fq_is_ext=False):
 def prove_phases(planner, trace, comp_expr, draws, blowup=4, folding=8, max_remainder_coeffs=64, grinding_bits=8, hash="sha256",
                  keep=False, ce_blowup=None, time_phases=True, field=GOLDILOCKS_FP):
     """trace: Matrix of Fp columns (2^k rows).  field: GOLDILOCKS_FP, or STARK252_FP (trace, draws and constraints over the 252-bit
-    field, LDE offset 3; commits with "sha256", "blake2s", "keccak256", "sha3_256" or the algebraic "poseidon252" -- RPO-256 absorbs Goldilocks elements,
+    field, LDE offset 3; commits with "sha256", "blake2s", "blake3_256", "keccak256", "sha3_256" or the algebraic "poseidon252" -- RPO-256 absorbs Goldilocks elements,
     Poseidon elements of the 252-bit field; a Poseidon prover grinds with SHA-256 over the last root's 32 bytes, as an RPO-256 one does).  ce_blowup: the AIR's ce_blowup_factor (src/air.rs:55-59; the constraint
     evaluation domain has trace_len * ce_blowup points, the composition trace ce_blowup columns); None = the LDE blow-up.
     Returns dict(roots=..., fri_roots=[...], remainder=GpuVec, nonce=int, queries=Queries, phases_ms={...}); with keep=True
@@ -518,7 +518,7 @@ def prove_phases(planner, trace, comp_expr, draws, blowup=4, folding=8, max_rema
     if field not in (GOLDILOCKS_FP, STARK252_FP):
         raise ValueError("prove_phases: field must be GOLDILOCKS_FP or STARK252_FP")
     if field == STARK252_FP and hash == "rpo256":
-        raise ValueError("prove_phases: RPO-256 absorbs Goldilocks elements; the 252-bit field commits with sha256, blake2s, keccak256 or sha3_256, "
+        raise ValueError("prove_phases: RPO-256 absorbs Goldilocks elements; the 252-bit field commits with sha256, blake2s, blake3_256, keccak256 or sha3_256, "
                          "or algebraically with poseidon252")
     if field != STARK252_FP and hash == "poseidon252":
         raise ValueError("prove_phases: poseidon252 absorbs elements of the 252-bit field: it needs field=STARK252_FP (Goldilocks commits algebraically with rpo256)")
@@ -682,7 +682,7 @@ def prove(planner, trace, comp_expr, nchallenges, hints, seed32, blowup=4, foldi
     if fq != field and (fq != GOLDILOCKS_FQ3 or field != GOLDILOCKS_FP):
         raise ValueError("prove: fq is the base field, or GOLDILOCKS_FQ3 over GOLDILOCKS_FP")
     if field == STARK252_FP and hash == "rpo256":
-        raise ValueError("prove: RPO-256 absorbs Goldilocks elements; the 252-bit field commits with sha256, blake2s, keccak256 or sha3_256, "
+        raise ValueError("prove: RPO-256 absorbs Goldilocks elements; the 252-bit field commits with sha256, blake2s, blake3_256, keccak256 or sha3_256, "
                          "or algebraically with poseidon252")
     if field != STARK252_FP and hash == "poseidon252":
         raise ValueError("prove: poseidon252 absorbs elements of the 252-bit field: it needs field=STARK252_FP (Goldilocks commits algebraically with rpo256)")

@@ -20,6 +20,7 @@
 pub mod plan;
 pub mod stage;
 pub mod sys;
+pub mod sys_blake3;
 pub mod sys_keccak;
 pub mod sys_ext;
 pub mod sys_gaps;
@@ -33,6 +34,6 @@ pub mod sys_sort;
 pub mod sys_transcript;
 pub mod utils;
 
-pub use plan::{evaluate_device, gen_rpo_merkle_tree, get_planner, lde_device, keccak_commit_device, poseidon252_commit_device, sha256_commit_device, GpuFft, GpuIfft, GpuRpo256ColumnMajor,
+pub use plan::{blake3_commit_device, evaluate_device, gen_rpo_merkle_tree, get_planner, lde_device, keccak_commit_device, poseidon252_commit_device, sha256_commit_device, GpuFft, GpuIfft, GpuRpo256ColumnMajor,
                GpuRpo256RowMajor, Planner};
 pub use utils::{bit_reverse_device, field_id, DeviceVec};

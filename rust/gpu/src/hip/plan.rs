@@ -2,6 +2,7 @@
 //! (reference: gpu/src/plan.rs:32-174, 236-325, 327-351, 464-469).  Same names, same signatures on host slices; the
 //! `*_device` methods are the resident variants the patched callers use (rust/patches/).
 use super::sys;
+use super::sys_blake3;
 use super::sys_keccak;
 use super::sys_poseidon;
 use super::utils::{field_id, DeviceVec};
@@ -158,6 +159,19 @@ pub fn keccak_commit_device<F: GpuField>(variant: c_int, columns: &[DeviceVec<F>
     let cols: Vec<*const c_void> = columns.iter().map(|c| c.device_ptr() as *const c_void).collect();
     sys::check(unsafe { sys_keccak::ms_keccak_rows(get_planner().ctx(), variant, field_id::<F>(), n, cols.as_ptr(), cols.len() as u32, leaves.device_ptr()) });
     sys::check(unsafe { sys_keccak::ms_keccak_merkle(get_planner().ctx(), variant, n, leaves.device_ptr() as *const c_void, nodes.device_ptr()) });
+    (leaves, nodes)
+}
+
+/// `sha256_commit_device` with H = unkeyed BLAKE3, 32-byte digest (`Hash::Blake3_256`; blake3::hash, Winterfell's `Blake3_256`): the leaves
+/// hash the bytes SHA-256 hashes (a row past 1024 bytes as BLAKE3's tree of chunks), a merge is the plain hash of 64 bytes, one
+/// compression.  -> (leaves, nodes); nodes[1] is the root.
+pub fn blake3_commit_device<F: GpuField>(columns: &[DeviceVec<F>]) -> (DeviceVec<[u8; 32]>, DeviceVec<[u8; 32]>) {
+    let n = columns[0].len();
+    let leaves = DeviceVec::<[u8; 32]>::with_len(n);
+    let nodes = DeviceVec::<[u8; 32]>::with_len(n);
+    let cols: Vec<*const c_void> = columns.iter().map(|c| c.device_ptr() as *const c_void).collect();
+    sys::check(unsafe { sys_blake3::ms_blake3_rows(get_planner().ctx(), field_id::<F>(), n, cols.as_ptr(), cols.len() as u32, leaves.device_ptr()) });
+    sys::check(unsafe { sys_blake3::ms_blake3_merkle(get_planner().ctx(), n, leaves.device_ptr() as *const c_void, nodes.device_ptr()) });
     (leaves, nodes)
 }
 

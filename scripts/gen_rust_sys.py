@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generate rust/gpu/src/hip/sys.rs -- the raw `extern "C"` bindings of the reference-side shim -- from
-include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h, sys_gaps.rs from include/ministark_hip_gaps.h, sys_join.rs from include/ministark_hip_join.h, sys_poseidon.rs from include/ministark_hip_poseidon.h and sys_hades_coin.rs from include/ministark_hip_hades_coin.h.  tests/test_rust_shim.py re-runs the parser and
+include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h, sys_gaps.rs from include/ministark_hip_gaps.h, sys_join.rs from include/ministark_hip_join.h, sys_poseidon.rs from include/ministark_hip_poseidon.h, sys_hades_coin.rs from include/ministark_hip_hades_coin.h and sys_blake3.rs from include/ministark_hip_blake3.h.  tests/test_rust_shim.py re-runs the parser and
 checks the committed file against the header, which stands in for compiling it (no Rust toolchain in the image).
 
     python scripts/gen_rust_sys.py            # rewrite rust/gpu/src/hip/sys.rs
@@ -34,6 +34,8 @@ POSEIDON_HEADER = os.path.join(ROOT, "include", "ministark_hip_poseidon.h")
 POSEIDON_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_poseidon.rs")
 HADES_COIN_HEADER = os.path.join(ROOT, "include", "ministark_hip_hades_coin.h")
 HADES_COIN_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_hades_coin.rs")
+BLAKE3_HEADER = os.path.join(ROOT, "include", "ministark_hip_blake3.h")
+BLAKE3_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_blake3.rs")
 
 BASE = {"int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "long": "c_long", "size_t": "usize", "uint64_t": "u64",
         "uint32_t": "u32", "char": "c_char", "unsigned char": "u8", "void": "c_void", "ms_ctx": "ms_ctx", "ms_ntt_plan": "ms_ntt_plan", "ms_xchg_op": "ms_xchg_op", "ms_p2p_op": "ms_p2p_op", "ms_jit_stats": "ms_jit_stats"}
@@ -416,6 +418,29 @@ def hades_coin_prototypes():
     return prototypes(text[text.index("#define MINISTARK_HIP_HADES_COIN_H"):])
 
 
+def render_blake3(protos):
+    """sys_blake3.rs: the entry points of include/ministark_hip_blake3.h (BLAKE3 commitments and proof-of-work), on sys.rs's types"""
+    lines = ["// GENERATED by scripts/gen_rust_sys.py from include/ministark_hip_blake3.h -- do not edit by hand.",
+             "// Raw bindings of the BLAKE3 layer of libministark_hip.so (INTEGRATION.md section 3i).",
+             "#![allow(non_camel_case_types)]",
+             "use core::ffi::{c_int, c_uint, c_void};",
+             "use super::sys::ms_ctx;",
+             "",
+             ] + [f"pub const {name}: c_int = {value};" for name, value in header_enums(BLAKE3_HEADER)] + [
+             "",
+             '#[link(name = "ministark_hip")]', 'extern "C" {']
+    for name, ret, plist in protos:
+        args = ", ".join(f"{(p + '_') if p in RUST_KEYWORDS else p}: {t}" for p, t in plist)
+        lines.append(f"    pub fn {name}({args})" + (f" -> {ret};" if ret else ";"))
+    lines += ["}", ""]
+    return "\n".join(lines)
+
+
+def blake3_prototypes():
+    text = open(BLAKE3_HEADER).read()
+    return prototypes(text[text.index("#define MINISTARK_HIP_BLAKE3_H"):])
+
+
 def main():
     protos = prototypes(open(HEADER).read())
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
@@ -466,6 +491,10 @@ def main():
     with open(HADES_COIN_OUT, "w") as f:
         f.write(render_hades_coin(protos))
     print(f"{len(protos)} prototypes -> {HADES_COIN_OUT}")
+    protos = blake3_prototypes()
+    with open(BLAKE3_OUT, "w") as f:
+        f.write(render_blake3(protos))
+    print(f"{len(protos)} prototypes -> {BLAKE3_OUT}")
 
 
 if __name__ == "__main__":
