@@ -13,5 +13,6 @@ from .api import (GOLDILOCKS_FP, GOLDILOCKS_FQ3, STARK252_FP, GL_GENERATOR, GL_P
 from .extension import (ExtColumn, LogUpColumn, LookupMissing, LookupReport, LookupTuple, build_extension_columns, build_logup_columns,  # noqa: F401
                         lookup_multiplicities, DeviceIndex, SortKey, SortReport, permute_columns, sort_rows,
                         GapError, GapPlan, GapReport, GapSpec, gap_fill, gap_plan,
-                        JoinReport, fetch_columns, join_rows)
+                        JoinReport, fetch_columns, join_rows,
+                        LimbReport, LimbSpec, RangeReport, RangeSet, limb_decompose, range_multiplicities)
 from .debug import ConstraintViolation, ValidationReport, compile_constraints, validate_constraints  # noqa: F401

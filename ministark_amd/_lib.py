@@ -75,6 +75,23 @@ class JoinReportRecord(ctypes.Structure):
                 ("pad", ctypes.c_uint32), ("duplicate_table_rows", ctypes.c_uint64), ("table_active", ctypes.c_uint64)]
 
 
+class LimbSpecRecord(ctypes.Structure):
+    """`ms_limb_spec` of include/ministark_hip_range.h."""
+    _fields_ = [("src", ctypes.c_int32), ("dst0", ctypes.c_int32), ("nlimbs", ctypes.c_int32), ("bits", ctypes.c_int32), ("mask", ctypes.c_int32), ("mask_col", ctypes.c_int32),
+                ("pad0", ctypes.c_int32), ("pad1", ctypes.c_int32)]
+
+
+class RangeSetRecord(ctypes.Structure):
+    """`ms_range_set` of include/ministark_hip_range.h."""
+    _fields_ = [("col", ctypes.c_int32), ("mask", ctypes.c_int32), ("mask_col", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class LimbReportRecord(ctypes.Structure):
+    """`ms_limb_report` of include/ministark_hip_range.h: what ms_limb_decompose found."""
+    _fields_ = [("overflow", ctypes.c_uint64), ("first_overflow_row", ctypes.c_uint64), ("first_overflow_spec", ctypes.c_uint32), ("pad", ctypes.c_uint32),
+                ("active", ctypes.c_uint64)]
+
+
 class SortKeyRecord(ctypes.Structure):
     """`ms_sort_key` of include/ministark_hip_sort.h."""
     _fields_ = [("cols", ctypes.c_int32 * 4), ("mask", ctypes.c_int32), ("mask_col", ctypes.c_int32), ("pad0", ctypes.c_int32), ("pad1", ctypes.c_int32)]
@@ -258,6 +275,11 @@ class Lib:
         join_sigs = {
             "ms_join_rows": (i, [vp, i, sz, c_void_pp, u, vp, sz, c_void_pp, u, u, vp, u, c_void_pp, vp]),
         }
+        # include/ministark_hip_range.h: range-check columns -- the limbs of a value column, the multiplicities of the table 0 .. 2^bits - 1
+        range_sigs = {
+            "ms_limb_decompose": (i, [vp, i, sz, c_void_pp, u, vp, u, vp]),
+            "ms_range_multiplicities": (i, [vp, i, sz, c_void_pp, u, u, vp, u, sz, vp, vp]),
+        }
         # include/ministark_hip_poseidon.h: Starknet's Poseidon over the 252-bit field -- the bulk permutation and the commitments
         poseidon_sigs = {
             "ms_poseidon252_permute": (i, [vp, sz, vp, vp]),
@@ -268,7 +290,7 @@ class Lib:
         self.optional = {}
         for name, (res, args) in (list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items())
                                   + list(logup_sigs.items()) + list(rpo_coin_sigs.items()) + list(lookup_sigs.items()) + list(sort_sigs.items()) + list(gap_sigs.items())
-                                  + list(join_sigs.items()) + list(poseidon_sigs.items()) + list(hades_coin_sigs.items()) + list(blake3_sigs.items())):
+                                  + list(join_sigs.items()) + list(poseidon_sigs.items()) + list(hades_coin_sigs.items()) + list(blake3_sigs.items()) + list(range_sigs.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -285,6 +307,7 @@ class Lib:
         self.poseidon_sigs = poseidon_sigs
         self.hades_coin_sigs = hades_coin_sigs
         self.blake3_sigs = blake3_sigs
+        self.range_sigs = range_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

@@ -6,6 +6,7 @@
 //   LookupTuple / lookup_multiplicities   the m column of a LogUp lookup, counted on the device (ministark_hip_lookup.h)
 //   SortKey / sort_rows / permute_columns   the rows of a table in key order (examples/brainfuck/vm.rs sort_by_key), on the device (ministark_hip_sort.h)
 //   join_rows / fetch_columns         for every row, the table row that holds its key, and that row's other columns: instruction fetch, ROM reads (ministark_hip_join.h)
+//   LimbSpec / limb_decompose / RangeSet / range_multiplicities   range checks: the limbs of a value column and the multiplicities of the table 0 .. 2^bits - 1 (ministark_hip_range.h)
 //   GapSpec / gap_plan / gap_fill     derive_memory_rows and pad_*_rows (examples/brainfuck/vm.rs:282-380): select, fill clock gaps, pad, on the device (ministark_hip_gaps.h)
 //   Queries                           src/trace.rs:113-157
 //   grind_proof_of_work               src/random.rs:48-55
@@ -25,6 +26,7 @@
 #include "../../../include/ministark_hip_sort.h"
 #include "../../../include/ministark_hip_gaps.h"
 #include "../../../include/ministark_hip_join.h"
+#include "../../../include/ministark_hip_range.h"
 #include <cstring>
 #include <stdint.h>
 // host arithmetic of the 252-bit field (points and offsets of its composer): the library's own fp252.h, kept inside ms:: so that its
@@ -303,6 +305,53 @@ inline std::pair<Matrix<B>, JoinReport> fetch_columns(const Matrix<B>& table, co
     for (auto& c : out.columns) to.push_back(c.ptr());
     check(ms_permute_columns(pl.ctx(), B::id, table.num_rows(), in.data(), to.data(), (unsigned)in.size(), rep.matches[0].index.ptr(), n));
     return {std::move(out), std::move(rep)};
+}
+
+// The limb columns of a range check in one asynchronous call (ms_limb_decompose): for every spec, columns dst0 .. dst0 + nlimbs - 1 of `trace`
+// get the limbs of column src -- limb j the bits [j * bits, (j + 1) * bits) of the canonical value -- and an inactive row zero limbs.  A value
+// that does not fit is counted in the report and still gets its low limbs.  mask as ExtColumn's.
+struct LimbSpec { int src = 0, dst0 = 0, nlimbs = 1, bits = 16, mask = MS_EXT_ALWAYS, mask_col = 0; };
+struct LimbReport {
+    GpuVec<Fp> buf;                                              // the ms_limb_report where the call wrote it
+    ms_limb_report read() const { const std::vector<uint64_t> w = buf.to_host(); ms_limb_report r; memcpy(&r, w.data(), sizeof r); return r; }   // a host wait
+};
+template <class B>
+inline LimbReport limb_decompose(Matrix<B>& trace, const std::vector<LimbSpec>& specs) {
+    Planner& pl = trace.planner();
+    if (specs.size() > (size_t)MS_RANGE_MAX_SPECS) throw std::invalid_argument("limb_decompose: at most 64 specs in one call");
+    std::vector<ms_limb_spec> recs;
+    for (auto& sp : specs) {
+        if (sp.bits < 1 || sp.bits > MS_RANGE_MAX_LIMB_BITS || sp.nlimbs < 1 || sp.nlimbs > MS_RANGE_MAX_LIMBS || (unsigned)(sp.nlimbs * sp.bits) > 64u * B::words)
+            throw std::invalid_argument("limb_decompose: 1 .. 256 limbs of 1 .. 32 bits, together no more than the bits of an element's words");
+        recs.push_back(ms_limb_spec{sp.src, sp.dst0, sp.nlimbs, sp.bits, sp.mask, sp.mask_col, 0, 0});
+    }
+    std::vector<void*> cols;
+    for (auto& c : trace.columns) cols.push_back(c.ptr());
+    LimbReport rep{GpuVec<Fp>(pl, sizeof(ms_limb_report) / 8)};
+    check(ms_limb_decompose(pl.ctx(), B::id, trace.num_rows(), cols.data(), (unsigned)cols.size(), recs.empty() ? nullptr : recs.data(), (unsigned)recs.size(), rep.buf.ptr()));
+    return rep;
+}
+
+// The m column of a range check in one asynchronous call (ms_range_multiplicities): m[j] = how many active rows of the `sets` hold the value
+// j, j < 2^bits, and zero from there to the end of m -- by direct indexing: no table column, no hash table.  A value that is not below 2^bits
+// is counted as missing in the report (an ms_lookup_report; duplicate_table_rows is 0).  m: at least 2^bits elements, possibly a column of
+// `trace` that no set and no mask names.
+struct RangeSet { int col = 0, mask = MS_EXT_ALWAYS, mask_col = 0; };
+using RangeReport = LookupReport;
+template <class B>
+inline RangeReport range_multiplicities(const Matrix<B>& trace, unsigned bits, const std::vector<RangeSet>& sets, GpuVec<B>& m) {
+    Planner& pl = trace.planner();
+    if (bits < 1 || bits > (unsigned)MS_RANGE_MAX_TABLE_BITS) throw std::invalid_argument("range_multiplicities: bits is 1 .. 24");
+    if (sets.size() > (size_t)MS_RANGE_MAX_SETS) throw std::invalid_argument("range_multiplicities: at most 64 sets in one call");
+    if (m.len() < ((size_t)1 << bits)) throw std::invalid_argument("range_multiplicities: m holds fewer elements than the table has rows");
+    std::vector<ms_range_set> recs;
+    for (auto& st : sets) recs.push_back(ms_range_set{st.col, st.mask, st.mask_col, 0});
+    std::vector<const void*> in;
+    for (auto& c : trace.columns) in.push_back(c.ptr());
+    RangeReport rep{GpuVec<Fp>(pl, sizeof(ms_lookup_report) / 8)};
+    check(ms_range_multiplicities(pl.ctx(), B::id, trace.num_rows(), in.data(), (unsigned)in.size(), bits, recs.empty() ? nullptr : recs.data(), (unsigned)recs.size(),
+                                  m.len(), m.ptr(), rep.buf.ptr()));
+    return rep;
 }
 
 // A table whose row count differs from its source's, derived where the source lies (ms_gap_plan, ms_gap_fill): the rows the mask lets

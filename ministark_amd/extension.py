@@ -28,13 +28,18 @@ an address, padding up to the trace length -- is `gap_plan` over ms_gap_plan and
 
 Fetching -- the instruction at an ip, the value at a ROM address, the result column of a function table -- is `join_rows` over ms_join_rows
 (include/ministark_hip_join.h): for every row, the index of the table row that holds its key, the table a matrix of its own; and
-`fetch_columns`, which hands that index to `permute_columns` and returns the table's other columns row by row."""
+`fetch_columns`, which hands that index to `permute_columns` and returns the table's other columns row by row.
+
+Range checks -- "this 32-bit value is two 16-bit limbs, and every limb is in [0, 2^16)" -- are `limb_decompose` over ms_limb_decompose and
+`range_multiplicities` over ms_range_multiplicities (include/ministark_hip_range.h): the limb columns written where the value column lies,
+and the multiplicities of the table 0 .. 2^bits - 1 counted by direct indexing, with no table column and no hash table."""
 import ctypes
 
 import numpy as np
 
-from ._lib import GapColumnRecord, GapReportRecord, GapSpecRecord, JoinReportRecord, LookupReportRecord, LookupTupleRecord, SortKeyRecord, SortReportRecord
-from .api import FIELD_WORDS, GOLDILOCKS_FP, DeviceBytes, GpuVec, Matrix, _ptr_array, f252_from_mont_limbs, gl_from_mont
+from ._lib import (GapColumnRecord, GapReportRecord, GapSpecRecord, JoinReportRecord, LimbReportRecord, LimbSpecRecord, LookupReportRecord, LookupTupleRecord,
+                   RangeSetRecord, SortKeyRecord, SortReportRecord)
+from .api import FIELD_WORDS, GOLDILOCKS_FP, STARK252_FP, DeviceBytes, GpuVec, Matrix, _ptr_array, f252_from_mont_limbs, gl_from_mont
 
 MAX_TERMS, MAX_COLUMNS, NONE = 8, 32, -1
 ROWS_PER_WORKGROUP = 1024             # msext::ROWS (csrc/ext_kernels.h): the rows one workgroup scans; tests/test_ext_abi.py keeps the two equal
@@ -44,6 +49,7 @@ LOGUP_MAX_FRACTIONS, LOGUP_MAX_COLUMNS = 4, 32
 LOOKUP_MAX_WIDTH, LOOKUP_MAX_SETS = 4, 8
 SORT_MAX_KEYS, PERMUTE_MAX_COLUMNS = 4, 128
 JOIN_MAX_WIDTH, JOIN_MAX_SETS, JOIN_NONE = 4, 8, 0xFFFFFFFF
+RANGE_MAX_SPECS, RANGE_MAX_SETS, RANGE_MAX_LIMBS, RANGE_MAX_LIMB_BITS, RANGE_MAX_TABLE_BITS = 64, 64, 256, 32, 24
 
 
 def _mask_words(who, mask):
@@ -477,6 +483,165 @@ def fetch_columns(planner, table, table_key, base, key, payload, out=None, check
     if check:
         report.check()
     return fetched, report
+
+
+def _canonical_at(planner, col, row):
+    """the canonical integer of element `row` of a base column (it downloads that element, nothing else)"""
+    V = FIELD_WORDS[col.field]
+    w = np.empty(V, dtype=np.uint64)
+    planner.lib.check(planner.lib.ms_download(planner.handle, w.ctypes.data, col.ptr + row * V * 8, V * 8))
+    return gl_from_mont(int(w[0])) if col.field == GOLDILOCKS_FP else f252_from_mont_limbs([int(x) for x in w])
+
+
+class LimbSpec:
+    """One decomposition: base column `src` -> the `nlimbs` columns dst0 .. dst0 + nlimbs - 1, limb j the bits [j * bits, (j + 1) * bits) of
+    the value's canonical integer.  mask: None (every row is active), ("nonzero", m) or ("zero", m), as for ExtColumn: an inactive row gets
+    zero limbs."""
+
+    def __init__(self, src, dst0, nlimbs, bits, mask=None):
+        self.src, self.dst0, self.nlimbs, self.bits, self.mask = int(src), int(dst0), int(nlimbs), int(bits), mask
+        if not 1 <= self.bits <= RANGE_MAX_LIMB_BITS:
+            raise ValueError(f"LimbSpec: a limb has 1 .. {RANGE_MAX_LIMB_BITS} bits, not {self.bits}")
+        if not 1 <= self.nlimbs <= RANGE_MAX_LIMBS:
+            raise ValueError(f"LimbSpec: 1 .. {RANGE_MAX_LIMBS} limbs, not {self.nlimbs}")
+        _mask_words("LimbSpec", mask)
+
+    def _record(self):
+        """the eight 32-bit words of ms_limb_spec: src, dst0, nlimbs, bits, mask, mask_col, pad0, pad1"""
+        mask = _mask_words("LimbSpec", self.mask)
+        return [self.src, self.dst0, self.nlimbs, self.bits, mask[0], mask[1], 0, 0]
+
+
+class RangeSet:
+    """One looked-up column of a range check: base column `col`; mask as for ExtColumn."""
+
+    def __init__(self, col, mask=None):
+        self.col, self.mask = int(col), mask
+        self.cols = [self.col]
+        _mask_words("RangeSet", mask)
+
+    def _record(self):
+        """the four 32-bit words of ms_range_set: col, mask, mask_col, pad"""
+        mask = _mask_words("RangeSet", self.mask)
+        return [self.col, mask[0], mask[1], 0]
+
+
+class LimbReport:
+    """What `limb_decompose` found: the ms_limb_report in device memory, downloaded (a host wait) when a field is first read.
+    .overflow: active rows whose value does not fit nlimbs * bits bits (they still got their low limbs); .first_overflow_spec /
+    .first_overflow_row: the smallest (spec, row) among them (0, 0 when there is none); .active: the rows the masks let through, over all
+    specs."""
+
+    def __init__(self, planner, buf, cols, specs):
+        self.planner, self.buf, self._cols, self._specs, self._rec = planner, buf, cols, specs, None
+
+    def _read(self):
+        if self._rec is None:
+            rec = LimbReportRecord()
+            self.planner.lib.check(self.planner.lib.ms_download(self.planner.handle, ctypes.addressof(rec), self.buf.ptr, ctypes.sizeof(rec)))
+            self._rec = rec
+        return self._rec
+
+    overflow = property(lambda self: int(self._read().overflow))
+    first_overflow_row = property(lambda self: int(self._read().first_overflow_row))
+    first_overflow_spec = property(lambda self: int(self._read().first_overflow_spec))
+    active = property(lambda self: int(self._read().active))
+
+    def __bool__(self):
+        return self.overflow == 0                # true when every value fits its limbs
+
+    def __repr__(self):
+        return (f"LimbReport(overflow={self.overflow}, first_overflow_spec={self.first_overflow_spec}, first_overflow_row={self.first_overflow_row}, "
+                f"active={self.active})")
+
+    def first_overflow_value(self):
+        """the canonical value of the first overflowing row (it downloads that element, nothing else), or None"""
+        if not self.overflow:
+            return None
+        return _canonical_at(self.planner, self._cols[self._specs[self.first_overflow_spec].src], self.first_overflow_row)
+
+    def check(self):
+        """raises LookupMissing, naming spec, row and the value, when a value does not fit its limbs"""
+        if self.overflow:
+            k, row, v = self.first_overflow_spec, self.first_overflow_row, self.first_overflow_value()
+            spec = self._specs[k]
+            err = LookupMissing(f"limb spec {k}, row {row}: the value {v} in base column {spec.src} does not fit {spec.nlimbs} limb(s) of {spec.bits} bits; "
+                                f"{self.overflow} row(s) in all do not fit")
+            err.set, err.spec, err.row, err.values, err.value, err.missing = k, k, row, [v], v, self.overflow
+            raise err
+        return self
+
+
+class RangeReport(LookupReport):
+    """What `range_multiplicities` found: a LookupReport (duplicate_table_rows is 0: the table 0 .. 2^bits - 1 has none) whose check()
+    names the set, the row and the value that is not below 2^bits."""
+
+    def __init__(self, planner, buf, cols, sets, bits):
+        super().__init__(planner, buf, cols, sets)
+        self.bits = bits
+
+    def __repr__(self):
+        return f"RangeReport(missing={self.missing}, first_missing_set={self.first_missing_set}, first_missing_row={self.first_missing_row})"
+
+    def check(self):
+        if self.missing:
+            s, row, vals = self.first_missing_set, self.first_missing_row, self.first_missing_values()
+            err = LookupMissing(f"range set {s}, row {row}: the value {vals[0]} in base column {self._lookups[s].col} is not below 2^{self.bits}; "
+                                f"{self.missing} looked-up row(s) in all are out of range")
+            err.set, err.row, err.values, err.missing = s, row, vals, self.missing
+            raise err
+        return self
+
+
+def limb_decompose(planner, trace, specs):
+    """Writes the limb columns of every LimbSpec into `trace` (a Matrix or a list of GpuVecs of one length and field) -> a LimbReport.
+    The destination columns of a spec are columns of the trace that no spec reads (as source or mask) and no other spec writes.
+    Enqueues and returns: no host wait until the report is read."""
+    cols = trace.columns if isinstance(trace, Matrix) else list(trace)
+    specs = list(specs)
+    n, field = _same_columns("limb_decompose", cols)
+    if field not in (GOLDILOCKS_FP, STARK252_FP):
+        raise ValueError("limb_decompose: the trace is over Fp or Fp252")
+    if len(specs) > RANGE_MAX_SPECS:
+        raise ValueError(f"limb_decompose: at most {RANGE_MAX_SPECS} specs in one call, not {len(specs)}")
+    for k, sp in enumerate(specs):
+        if sp.nlimbs * sp.bits > 64 * FIELD_WORDS[field]:
+            raise ValueError(f"limb_decompose: spec {k}: {sp.nlimbs} limbs of {sp.bits} bits are more than the {64 * FIELD_WORDS[field]} bits of an element's words")
+    buf = GpuVec(planner, ctypes.sizeof(LimbReportRecord) // 8, GOLDILOCKS_FP)
+    rec = np.array([sp._record() for sp in specs], dtype=np.int32).reshape(-1, 8)
+    assert rec.nbytes == len(specs) * ctypes.sizeof(LimbSpecRecord)
+    L = planner.lib
+    L.check(L.ms_limb_decompose(planner.handle, field, n, _ptr_array(cols), len(cols), rec.ctypes.data if rec.size else None, len(specs), buf.ptr))
+    return LimbReport(planner, buf, cols, specs)
+
+
+def range_multiplicities(planner, trace, bits, sets, out=None, n_m=None):
+    """-> (m, report): m[j] = how many active rows of the `sets` (RangeSet records) hold the value j, for j < 2^bits, and zero from there to
+    n_m (default: the length of `out`, or of the trace), as elements of the base field.  out: the GpuVec to fill (its first n_m elements)
+    -- it may be a column of `trace` that no set and no mask names, the trace's own m column -- or None for a new one.  report: a
+    RangeReport; a value that is not below 2^bits is counted there as missing.  Enqueues and returns: no host wait until it is read."""
+    cols = trace.columns if isinstance(trace, Matrix) else list(trace)
+    sets, bits = list(sets), int(bits)
+    n, field = _same_columns("range_multiplicities", cols)
+    if not 1 <= bits <= RANGE_MAX_TABLE_BITS:
+        raise ValueError(f"range_multiplicities: bits is 1 .. {RANGE_MAX_TABLE_BITS}, not {bits}")
+    if len(sets) > RANGE_MAX_SETS:
+        raise ValueError(f"range_multiplicities: at most {RANGE_MAX_SETS} sets in one call, not {len(sets)}")
+    if n_m is None:
+        n_m = len(out) if out is not None else n
+    n_m = int(n_m)
+    if n_m < (1 << bits):
+        raise ValueError(f"range_multiplicities: m holds {n_m} elements, fewer than the 2^{bits} rows of the table")
+    m = GpuVec(planner, n_m, field) if out is None else out
+    if len(m) < n_m or m.field != field:
+        raise ValueError("range_multiplicities: `out` is a column of the base field of at least n_m elements")
+    buf = GpuVec(planner, ctypes.sizeof(LookupReportRecord) // 8, GOLDILOCKS_FP)
+    rec = np.array([s._record() for s in sets], dtype=np.int32).reshape(-1, 4)
+    assert rec.nbytes == len(sets) * ctypes.sizeof(RangeSetRecord)
+    L = planner.lib
+    L.check(L.ms_range_multiplicities(planner.handle, field, n, _ptr_array(cols), len(cols), bits, rec.ctypes.data if rec.size else None, len(sets),
+                                      n_m, m.ptr, buf.ptr))
+    return m, RangeReport(planner, buf, cols, sets, bits)
 
 
 GAP_MAX_GROUP, GAP_MAX_COLUMNS = 3, 128

@@ -296,6 +296,68 @@ def lookup_air(n):
     return comp, ce, ncoeffs, 2, columns
 
 
+def range_trace(n, bits, seed):
+    """A valid base trace of `range_air`: columns x, l0, l1, t, m as canonical integers.  x is drawn below 2^(2 bits), l0 and l1 are its
+    low and high limbs of `bits` bits, t[j] = min(j, 2^bits - 1) is the table 0 .. 2^bits - 1 padded to n rows by repeating its last row,
+    and m[j] counts how often j occurs in l0 and l1 together (zero from 2^bits on).  n >= 2^bits."""
+    assert 1 <= bits <= 16 and n >= (1 << bits)
+    rng = np.random.default_rng(seed)
+    x = [int(v) for v in rng.integers(0, 1 << (2 * bits), size=n, dtype=np.uint64)]
+    l0, l1 = [v & ((1 << bits) - 1) for v in x], [v >> bits for v in x]
+    m = [0] * n
+    for v in l0 + l1:
+        m[v] += 1
+    return [x, l0, l1, [min(j, (1 << bits) - 1) for j in range(n)], m]
+
+
+def range_trace_on_device(planner, n, bits, seed, check=False, x=None):
+    """`range_trace(n, bits, seed)` built where the trace lies: x and t are uploaded beside three zero columns, ms_limb_decompose
+    (extension.limb_decompose) writes l0 and l1, and ms_range_multiplicities (extension.range_multiplicities) counts both limb columns into
+    m in place -- by direct indexing: t is a column of the AIR, not an input of the count.  Nothing is downloaded.
+    -> the base trace as a Matrix of five Fp columns, equal to the uploaded `range_trace` in every word.  check: read both calls' reports
+    (host waits) and raise LookupMissing if a value does not fit two limbs, or a limb is not below 2^bits.
+    x: the values to decompose, in place of the drawn ones (canonical integers)."""
+    from .extension import LimbSpec, RangeSet, limb_decompose, range_multiplicities
+    cols = range_trace(n, bits, seed)
+    words = lambda c: to_mont_words(GOLDILOCKS_FP, c).ravel()
+    zero = np.zeros(n, dtype=np.uint64)
+    trace = Matrix.from_numpy(planner, [words(cols[0] if x is None else x), zero, zero, words(cols[3]), zero], GOLDILOCKS_FP)
+    limbs = limb_decompose(planner, trace, [LimbSpec(0, 1, 2, bits)])
+    _, counts = range_multiplicities(planner, trace, bits, [RangeSet(1), RangeSet(2)], out=trace.columns[4])
+    if check:
+        limbs.check()
+        counts.check()
+    return trace
+
+
+def range_air_constraints(n, bits):
+    """The three constraints of `range_air`, in its order: the recomposition x = l0 + 2^bits l1 on every row, the boundary S = 0 at row 0,
+    and the LogUp transition, both transitions over the full zerofier X^n - 1."""
+    x = E.X()
+    cur, nxt, ch = (lambda k: E.Trace(k, 0)), (lambda k: E.Trace(k, 1)), E.Challenge
+    S = 5
+    zerofier = x ** n - E.Constant(1)
+    dt, d0, d1 = ch(0) - cur(3), ch(0) - cur(1), ch(0) - cur(2)
+    return [(cur(0) - cur(1) - E.Constant(1 << bits) * cur(2)) / zerofier,
+            cur(S) / (x - E.Constant(1)),
+            ((nxt(S) - cur(S)) * dt * d0 * d1 - cur(4) * d0 * d1 + dt * d1 + dt * d0) / zerofier]
+
+
+def range_air(n, bits):
+    """A range-checked AIR, valid on `range_trace`: x is two limbs of `bits` bits, and both limbs are rows of the table t = 0 .. 2^bits - 1,
+    which is looked up m times.  Base columns 0..4 = x, l0, l1, t, m; extension column 5 = S; challenge 0 = alpha:
+        x - l0 - 2^bits l1 = 0,        S' = S + m / (alpha - t) - 1 / (alpha - l0) - 1 / (alpha - l1)
+    S = 0 at row 0, and the transition, cleared of its three denominators, on EVERY row (divided by X^n - 1): Trace(S, 1) of the last row is S
+    of row 0, so the wrap-around is the statement that the fractions sum to zero and there is no terminal constraint, as in `lookup_air`.
+    The cleared transition has degree 4: ce_blowup comes out as 4, so `prove` needs blowup >= 4.
+    -> (composition constraint, ce_blowup, number of composition coefficients, number of AIR challenges 1, the LogUpColumn record)."""
+    from .extension import LogUpColumn
+    comp, ce, ncoeffs = composition_constraint(n, range_air_constraints(n, bits), num_air_challenges=1)
+    den = lambda c: [(+1, 0, None), (-1, None, c)]
+    columns = [LogUpColumn(0, [([(+1, None, 4)], den(3)), ([(-1, None, None)], den(1)), ([(-1, None, None)], den(2))])]
+    return comp, ce, ncoeffs, 1, columns
+
+
 def memory_processor_rows(steps, seed):
     """The processor table of a small tape machine, as canonical integers: columns cycle, mp, mem_val, instr; `steps` executed rows and the
     final state row, whose instr is 0.  Instructions 1..4, drawn at random: increment and decrement the cell under the pointer (mod p), move

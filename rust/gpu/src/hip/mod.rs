@@ -29,6 +29,7 @@ pub mod sys_join;
 pub mod sys_logup;
 pub mod sys_lookup;
 pub mod sys_poseidon;
+pub mod sys_range;
 pub mod sys_rpo_coin;
 pub mod sys_sort;
 pub mod sys_transcript;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generate rust/gpu/src/hip/sys.rs -- the raw `extern "C"` bindings of the reference-side shim -- from
-include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h, sys_gaps.rs from include/ministark_hip_gaps.h, sys_join.rs from include/ministark_hip_join.h, sys_poseidon.rs from include/ministark_hip_poseidon.h, sys_hades_coin.rs from include/ministark_hip_hades_coin.h and sys_blake3.rs from include/ministark_hip_blake3.h.  tests/test_rust_shim.py re-runs the parser and
+include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h, sys_gaps.rs from include/ministark_hip_gaps.h, sys_join.rs from include/ministark_hip_join.h, sys_poseidon.rs from include/ministark_hip_poseidon.h, sys_hades_coin.rs from include/ministark_hip_hades_coin.h sys_blake3.rs from include/ministark_hip_blake3.h and sys_range.rs from include/ministark_hip_range.h.  tests/test_rust_shim.py re-runs the parser and
 checks the committed file against the header, which stands in for compiling it (no Rust toolchain in the image).
 
     python scripts/gen_rust_sys.py            # rewrite rust/gpu/src/hip/sys.rs
@@ -36,6 +36,8 @@ HADES_COIN_HEADER = os.path.join(ROOT, "include", "ministark_hip_hades_coin.h")
 HADES_COIN_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_hades_coin.rs")
 BLAKE3_HEADER = os.path.join(ROOT, "include", "ministark_hip_blake3.h")
 BLAKE3_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_blake3.rs")
+RANGE_HEADER = os.path.join(ROOT, "include", "ministark_hip_range.h")
+RANGE_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_range.rs")
 
 BASE = {"int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "long": "c_long", "size_t": "usize", "uint64_t": "u64",
         "uint32_t": "u32", "char": "c_char", "unsigned char": "u8", "void": "c_void", "ms_ctx": "ms_ctx", "ms_ntt_plan": "ms_ntt_plan", "ms_xchg_op": "ms_xchg_op", "ms_p2p_op": "ms_p2p_op", "ms_jit_stats": "ms_jit_stats"}
@@ -441,6 +443,33 @@ def blake3_prototypes():
     return prototypes(text[text.index("#define MINISTARK_HIP_BLAKE3_H"):])
 
 
+def render_range(protos):
+    """sys_range.rs: the entry points of include/ministark_hip_range.h (range-check columns: limbs and direct-indexed multiplicities), on
+    sys.rs's types; the count's report is sys_lookup.rs's ms_lookup_report and the mask kinds are sys_ext.rs's"""
+    lines = ["// GENERATED by scripts/gen_rust_sys.py from include/ministark_hip_range.h -- do not edit by hand.",
+             "// Raw bindings of the range-check layer of libministark_hip.so (INTEGRATION.md section 3e); ms_lookup_report: sys_lookup.rs; the MS_EXT_* mask kinds: sys_ext.rs.",
+             "#![allow(non_camel_case_types)]",
+             "use core::ffi::{c_int, c_uint, c_void};",
+             "use super::sys::ms_ctx;",
+             "",
+             "#[repr(C)] #[derive(Clone, Copy, Debug, Default)] pub struct ms_limb_spec { pub src: i32, pub dst0: i32, pub nlimbs: i32, pub bits: i32, pub mask: i32, pub mask_col: i32, pub pad0: i32, pub pad1: i32 }",
+             "#[repr(C)] #[derive(Clone, Copy, Debug, Default)] pub struct ms_range_set { pub col: i32, pub mask: i32, pub mask_col: i32, pub pad: i32 }",
+             "#[repr(C)] #[derive(Clone, Copy, Debug, Default)] pub struct ms_limb_report { pub overflow: u64, pub first_overflow_row: u64, pub first_overflow_spec: u32, pub pad: u32, pub active: u64 }",
+             ] + [f"pub const {name}: c_int = {value};" for name, value in header_enums(RANGE_HEADER)] + [
+             "",
+             '#[link(name = "ministark_hip")]', 'extern "C" {']
+    for name, ret, plist in protos:
+        args = ", ".join(f"{(p + '_') if p in RUST_KEYWORDS else p}: {t}" for p, t in plist)
+        lines.append(f"    pub fn {name}({args})" + (f" -> {ret};" if ret else ";"))
+    lines += ["}", ""]
+    return "\n".join(lines)
+
+
+def range_prototypes():
+    text = open(RANGE_HEADER).read()
+    return prototypes(text[text.index("#define MINISTARK_HIP_RANGE_H"):])
+
+
 def main():
     protos = prototypes(open(HEADER).read())
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
@@ -495,6 +524,10 @@ def main():
     with open(BLAKE3_OUT, "w") as f:
         f.write(render_blake3(protos))
     print(f"{len(protos)} prototypes -> {BLAKE3_OUT}")
+    protos = range_prototypes()
+    with open(RANGE_OUT, "w") as f:
+        f.write(render_range(protos))
+    print(f"{len(protos)} prototypes -> {RANGE_OUT}")
 
 
 if __name__ == "__main__":
