@@ -14,5 +14,6 @@ from .extension import (ExtColumn, LogUpColumn, LookupMissing, LookupReport, Loo
                         lookup_multiplicities, DeviceIndex, SortKey, SortReport, permute_columns, sort_rows,
                         GapError, GapPlan, GapReport, GapSpec, gap_fill, gap_plan,
                         JoinReport, fetch_columns, join_rows,
-                        LimbReport, LimbSpec, RangeReport, RangeSet, limb_decompose, range_multiplicities)
+                        LimbReport, LimbSpec, RangeReport, RangeSet, limb_decompose, range_multiplicities,
+                        BitwiseReport, BitwiseSet, BitwiseSpec, bitwise_columns, bitwise_multiplicities, bitwise_table)
 from .debug import ConstraintViolation, ValidationReport, compile_constraints, validate_constraints  # noqa: F401

@@ -92,6 +92,18 @@ class LimbReportRecord(ctypes.Structure):
                 ("active", ctypes.c_uint64)]
 
 
+class BitwiseSpecRecord(ctypes.Structure):
+    """`ms_bitwise_spec` of include/ministark_hip_bitwise.h."""
+    _fields_ = [("op", ctypes.c_int32), ("a", ctypes.c_int32), ("b", ctypes.c_int32), ("dst", ctypes.c_int32), ("width", ctypes.c_int32), ("mask", ctypes.c_int32),
+                ("mask_col", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class BitwiseSetRecord(ctypes.Structure):
+    """`ms_bitwise_set` of include/ministark_hip_bitwise.h."""
+    _fields_ = [("op", ctypes.c_int32), ("a", ctypes.c_int32), ("b", ctypes.c_int32), ("c", ctypes.c_int32), ("nlimbs", ctypes.c_int32), ("mask", ctypes.c_int32),
+                ("mask_col", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 class SortKeyRecord(ctypes.Structure):
     """`ms_sort_key` of include/ministark_hip_sort.h."""
     _fields_ = [("cols", ctypes.c_int32 * 4), ("mask", ctypes.c_int32), ("mask_col", ctypes.c_int32), ("pad0", ctypes.c_int32), ("pad1", ctypes.c_int32)]
@@ -280,6 +292,12 @@ class Lib:
             "ms_limb_decompose": (i, [vp, i, sz, c_void_pp, u, vp, u, vp]),
             "ms_range_multiplicities": (i, [vp, i, sz, c_void_pp, u, u, vp, u, sz, vp, vp]),
         }
+        # include/ministark_hip_bitwise.h: bitwise-operation columns -- a op b, the table over limb pairs, its direct-indexed multiplicities
+        bitwise_sigs = {
+            "ms_bitwise_columns": (i, [vp, i, sz, c_void_pp, u, vp, u, vp]),
+            "ms_bitwise_table": (i, [vp, i, u, vp, u, sz, vp, vp, vp, vp]),
+            "ms_bitwise_multiplicities": (i, [vp, i, sz, c_void_pp, u, u, vp, u, vp, u, sz, vp, vp]),
+        }
         # include/ministark_hip_poseidon.h: Starknet's Poseidon over the 252-bit field -- the bulk permutation and the commitments
         poseidon_sigs = {
             "ms_poseidon252_permute": (i, [vp, sz, vp, vp]),
@@ -290,7 +308,7 @@ class Lib:
         self.optional = {}
         for name, (res, args) in (list(sigs.items()) + list(transcript_sigs.items()) + list(keccak_sigs.items()) + list(ext_sigs.items())
                                   + list(logup_sigs.items()) + list(rpo_coin_sigs.items()) + list(lookup_sigs.items()) + list(sort_sigs.items()) + list(gap_sigs.items())
-                                  + list(join_sigs.items()) + list(poseidon_sigs.items()) + list(hades_coin_sigs.items()) + list(blake3_sigs.items()) + list(range_sigs.items())):
+                                  + list(join_sigs.items()) + list(poseidon_sigs.items()) + list(hades_coin_sigs.items()) + list(blake3_sigs.items()) + list(range_sigs.items()) + list(bitwise_sigs.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -308,6 +326,7 @@ class Lib:
         self.hades_coin_sigs = hades_coin_sigs
         self.blake3_sigs = blake3_sigs
         self.range_sigs = range_sigs
+        self.bitwise_sigs = bitwise_sigs
 
     def declare(self, name, res, args):
         fn = getattr(self.L, name)

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libministark_hip.so")
-SOURCES = ["ms_core.cpp", "ms_ntt_plan.cpp", "ms_ntt.cpp", "ms_ntt252.cpp", "ms_stage.cpp", "ms_hash.cpp", "ms_eval.cpp", "ms_deep.cpp", "ms_comm.cpp", "ms_validate.cpp", "ms_blake2s.cpp", "ms_canon.cpp", "ms_coin.cpp", "ms_keccak.cpp", "ms_ext.cpp", "ms_logup.cpp", "ms_rpo_coin.cpp", "ms_lookup.cpp", "ms_sort.cpp", "ms_gaps.cpp", "ms_join.cpp", "ms_poseidon.cpp", "ms_hades_coin.cpp", "ms_blake3.cpp", "ms_range.cpp"]
+SOURCES = ["ms_core.cpp", "ms_ntt_plan.cpp", "ms_ntt.cpp", "ms_ntt252.cpp", "ms_stage.cpp", "ms_hash.cpp", "ms_eval.cpp", "ms_deep.cpp", "ms_comm.cpp", "ms_validate.cpp", "ms_blake2s.cpp", "ms_canon.cpp", "ms_coin.cpp", "ms_keccak.cpp", "ms_ext.cpp", "ms_logup.cpp", "ms_rpo_coin.cpp", "ms_lookup.cpp", "ms_sort.cpp", "ms_gaps.cpp", "ms_join.cpp", "ms_poseidon.cpp", "ms_hades_coin.cpp", "ms_blake3.cpp", "ms_range.cpp", "ms_bitwise.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-Wall", "-Wno-unused-function"]
 OBJDIR = os.path.join(HERE, "_obj")
@@ -37,6 +37,7 @@ def _deps():
     out.append(os.path.join(ROOT, "include", "ministark_hip_hades_coin.h"))
     out.append(os.path.join(ROOT, "include", "ministark_hip_blake3.h"))
     out.append(os.path.join(ROOT, "include", "ministark_hip_range.h"))
+    out.append(os.path.join(ROOT, "include", "ministark_hip_bitwise.h"))
     return out
 
 
@@ -74,7 +75,7 @@ def source_hash(cmd):
 
 def build(force=False, verbose=True):
     """One hipcc -c per translation unit, in parallel, then one link: the library is one unit per area (context / NTT plans / Goldilocks NTT and LDE / 252-bit NTT /
-    stages / hashes / BLAKE2s / Keccak / BLAKE3 / public coin / extension columns / LogUp columns / lookup multiplicities / row sort / padded tables / row join / range checks / Poseidon / Poseidon coin / RPO-256 coin / constraint evaluation / validation / DEEP / RCCL exchange) instead of one 2 400-line file."""
+    stages / hashes / BLAKE2s / Keccak / BLAKE3 / public coin / extension columns / LogUp columns / lookup multiplicities / row sort / padded tables / row join / range checks / bitwise columns / Poseidon / Poseidon coin / RPO-256 coin / constraint evaluation / validation / DEEP / RCCL exchange) instead of one 2 400-line file."""
     from concurrent.futures import ThreadPoolExecutor
     embed_headers()
     extra = os.environ.get("MS_HIPCC_FLAGS", "").split()

@@ -7,6 +7,7 @@
 //   SortKey / sort_rows / permute_columns   the rows of a table in key order (examples/brainfuck/vm.rs sort_by_key), on the device (ministark_hip_sort.h)
 //   join_rows / fetch_columns         for every row, the table row that holds its key, and that row's other columns: instruction fetch, ROM reads (ministark_hip_join.h)
 //   LimbSpec / limb_decompose / RangeSet / range_multiplicities   range checks: the limbs of a value column and the multiplicities of the table 0 .. 2^bits - 1 (ministark_hip_range.h)
+//   BitwiseSpec / bitwise_columns / bitwise_table / BitwiseSet / bitwise_multiplicities   a AND / OR / XOR b as a column, the table over limb pairs and its multiplicities (ministark_hip_bitwise.h)
 //   GapSpec / gap_plan / gap_fill     derive_memory_rows and pad_*_rows (examples/brainfuck/vm.rs:282-380): select, fill clock gaps, pad, on the device (ministark_hip_gaps.h)
 //   Queries                           src/trace.rs:113-157
 //   grind_proof_of_work               src/random.rs:48-55
@@ -27,6 +28,7 @@
 #include "../../../include/ministark_hip_gaps.h"
 #include "../../../include/ministark_hip_join.h"
 #include "../../../include/ministark_hip_range.h"
+#include "../../../include/ministark_hip_bitwise.h"
 #include <cstring>
 #include <stdint.h>
 // host arithmetic of the 252-bit field (points and offsets of its composer): the library's own fp252.h, kept inside ms:: so that its
@@ -351,6 +353,70 @@ inline RangeReport range_multiplicities(const Matrix<B>& trace, unsigned bits, c
     RangeReport rep{GpuVec<Fp>(pl, sizeof(ms_lookup_report) / 8)};
     check(ms_range_multiplicities(pl.ctx(), B::id, trace.num_rows(), in.data(), (unsigned)in.size(), bits, recs.empty() ? nullptr : recs.data(), (unsigned)recs.size(),
                                   m.len(), m.ptr(), rep.buf.ptr()));
+    return rep;
+}
+
+// The result columns of bitwise operations in one asynchronous call (ms_bitwise_columns): for every spec, column dst of `trace` gets
+// (a mod 2^width) op (b mod 2^width) on the canonical integers of columns a and b -- op MS_BIT_AND, MS_BIT_OR or MS_BIT_XOR, a == b allowed --
+// and an inactive row zero.  An operand that does not fit `width` bits is counted in the report (an ms_limb_report).  mask as ExtColumn's.
+struct BitwiseSpec { int op = MS_BIT_XOR, a = 0, b = 0, dst = 0, width = 32, mask = MS_EXT_ALWAYS, mask_col = 0; };
+template <class B> inline unsigned bitwise_wmax() { return B::words == 1 ? 63u : 251u; }          // 2^wmax: the widest power of two below the modulus
+template <class B>
+inline LimbReport bitwise_columns(Matrix<B>& trace, const std::vector<BitwiseSpec>& specs) {
+    Planner& pl = trace.planner();
+    if (specs.size() > (size_t)MS_BITWISE_MAX_SPECS) throw std::invalid_argument("bitwise_columns: at most 64 specs in one call");
+    std::vector<ms_bitwise_spec> recs;
+    for (auto& sp : specs) {
+        if (sp.width < 1 || (unsigned)sp.width > bitwise_wmax<B>()) throw std::invalid_argument("bitwise_columns: an operand has 1 .. 63 bits over Fp, 1 .. 251 over Fp252");
+        recs.push_back(ms_bitwise_spec{sp.op, sp.a, sp.b, sp.dst, sp.width, sp.mask, sp.mask_col, 0});
+    }
+    std::vector<void*> cols;
+    for (auto& c : trace.columns) cols.push_back(c.ptr());
+    LimbReport rep{GpuVec<Fp>(pl, sizeof(ms_limb_report) / 8)};
+    check(ms_bitwise_columns(pl.ctx(), B::id, trace.num_rows(), cols.data(), (unsigned)cols.size(), recs.empty() ? nullptr : recs.data(), (unsigned)recs.size(), rep.buf.ptr()));
+    return rep;
+}
+
+// The table (op, x, y, x op y) over all pairs of `bits`-bit limbs, op by op in the order of `ops`, written where it is used
+// (ms_bitwise_table) and padded to the columns' length by repeating its last row.  top: the op column, or null for none.
+inline size_t bitwise_table_rows(unsigned bits, const std::vector<int>& ops) {
+    if (bits < 1 || bits > (unsigned)MS_BITWISE_MAX_BITS || ops.empty() || ops.size() > (size_t)MS_BITWISE_MAX_OPS || (ops.size() << (2 * bits)) > ((size_t)1 << MS_BITWISE_MAX_TABLE_LOG))
+        throw std::invalid_argument("bitwise table: bits is 1 .. 12, 1 .. 3 ops, at most 2^24 rows");
+    return ops.size() << (2 * bits);
+}
+template <class B>
+inline void bitwise_table(unsigned bits, const std::vector<int>& ops, GpuVec<B>* top, GpuVec<B>& tx, GpuVec<B>& ty, GpuVec<B>& tz) {
+    Planner& pl = tx.planner();
+    const size_t T = bitwise_table_rows(bits, ops), n_t = tx.len();
+    if (n_t < T || ty.len() != n_t || tz.len() != n_t || (top && top->len() != n_t)) throw std::invalid_argument("bitwise_table: columns of one length, at least the table's rows");
+    std::vector<int32_t> codes(ops.begin(), ops.end());
+    check(ms_bitwise_table(pl.ctx(), B::id, bits, codes.data(), (unsigned)codes.size(), n_t, top ? top->ptr() : nullptr, tx.ptr(), ty.ptr(), tz.ptr()));
+}
+
+// The m column of a bitwise lookup in one asynchronous call (ms_bitwise_multiplicities): m[slot * 4^bits + (x << bits) + y] = how many
+// limb pairs (x, y) the active rows of the `sets` whose op stands at `slot` of `ops` hold, counted from the word columns a, b (and checked
+// against c, unless c is -1); zero from the table's end to the end of m.  A row with an operand not below 2^(nlimbs * bits), or with
+// c != a op b, is counted as missing in the report (an ms_lookup_report) and none of its limbs is counted.
+struct BitwiseSet { int op = MS_BIT_XOR, a = 0, b = 0, c = -1, nlimbs = 1, mask = MS_EXT_ALWAYS, mask_col = 0; };
+using BitwiseReport = LookupReport;
+template <class B>
+inline BitwiseReport bitwise_multiplicities(const Matrix<B>& trace, unsigned bits, const std::vector<int>& ops, const std::vector<BitwiseSet>& sets, GpuVec<B>& m) {
+    Planner& pl = trace.planner();
+    const size_t T = bitwise_table_rows(bits, ops);
+    if (sets.size() > (size_t)MS_BITWISE_MAX_SETS) throw std::invalid_argument("bitwise_multiplicities: at most 64 sets in one call");
+    if (m.len() < T) throw std::invalid_argument("bitwise_multiplicities: m holds fewer elements than the table has rows");
+    std::vector<ms_bitwise_set> recs;
+    for (auto& st : sets) {
+        if (st.nlimbs < 1 || st.nlimbs > MS_BITWISE_MAX_LIMBS || (unsigned)st.nlimbs * bits > bitwise_wmax<B>())
+            throw std::invalid_argument("bitwise_multiplicities: 1 .. 256 limbs, together no more than 63 bits over Fp, 251 over Fp252");
+        recs.push_back(ms_bitwise_set{st.op, st.a, st.b, st.c, st.nlimbs, st.mask, st.mask_col, 0});
+    }
+    std::vector<int32_t> codes(ops.begin(), ops.end());
+    std::vector<const void*> in;
+    for (auto& c : trace.columns) in.push_back(c.ptr());
+    BitwiseReport rep{GpuVec<Fp>(pl, sizeof(ms_lookup_report) / 8)};
+    check(ms_bitwise_multiplicities(pl.ctx(), B::id, trace.num_rows(), in.data(), (unsigned)in.size(), bits, codes.data(), (unsigned)codes.size(),
+                                    recs.empty() ? nullptr : recs.data(), (unsigned)recs.size(), m.len(), m.ptr(), rep.buf.ptr()));
     return rep;
 }
 

@@ -1,5 +1,5 @@
 // Internal declarations shared by the translation units of libministark_hip.so (ms_core / ms_ntt_plan / ms_ntt / ms_ntt252 / ms_stage / ms_hash / ms_eval / ms_deep /
-// ms_comm / ms_validate / ms_blake2s / ms_canon / ms_coin / ms_keccak / ms_ext / ms_logup / ms_rpo_coin / ms_lookup / ms_sort / ms_gaps / ms_join / ms_poseidon / ms_blake3 / ms_range .cpp,
+// ms_comm / ms_validate / ms_blake2s / ms_canon / ms_coin / ms_keccak / ms_ext / ms_logup / ms_rpo_coin / ms_lookup / ms_sort / ms_gaps / ms_join / ms_poseidon / ms_blake3 / ms_range / ms_bitwise .cpp,
 // the SOURCES of build.py): the context, the plan object and what the three NTT units share, error plumbing, the coset-offset decoders, pooled
 // scratch, the checked mode's scans and the base-column arguments of the trace-table entry points.  Not part of the C ABI.
 #pragma once
@@ -222,7 +222,7 @@ static inline int field_of_words(unsigned V) { return V == 1 ? MS_GOLDILOCKS_FP 
 // d_base[c] for c in `used` alone (what a call NAMES; the rest of d_base may hold anything); the refusal reports the caller's own column index
 int canon_named(ms_ctx* ctx, const char* entry, int field, size_t n, const void* const* d_base, const std::vector<unsigned>& used, const char* arg = "d_base");
 
-// ms_core.cpp: the base-column table (d_base, nbase) of a trace-table entry point (ms_ext / ms_logup / ms_lookup / ms_sort / ms_gaps / ms_join / ms_range .cpp):
+// ms_core.cpp: the base-column table (d_base, nbase) of a trace-table entry point (ms_ext / ms_logup / ms_lookup / ms_sort / ms_gaps / ms_join / ms_range / ms_bitwise .cpp):
 // resolves the column indices of the caller's records to addresses, refuses the ones out of range, and keeps the list of the columns
 // named, in the order first named -- what the overlap checks and canon_named go through.  `what` / `who` open the refusal after
 // "<entry>: " and end in a space or in ": " ("key ", "lookup set 1: ", "column 3: term ").

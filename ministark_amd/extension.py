@@ -32,12 +32,17 @@ Fetching -- the instruction at an ip, the value at a ROM address, the result col
 
 Range checks -- "this 32-bit value is two 16-bit limbs, and every limb is in [0, 2^16)" -- are `limb_decompose` over ms_limb_decompose and
 `range_multiplicities` over ms_range_multiplicities (include/ministark_hip_range.h): the limb columns written where the value column lies,
-and the multiplicities of the table 0 .. 2^bits - 1 counted by direct indexing, with no table column and no hash table."""
+and the multiplicities of the table 0 .. 2^bits - 1 counted by direct indexing, with no table column and no hash table.
+
+Bitwise operations -- the one family of columns no constraint program can compute -- are `bitwise_columns` over ms_bitwise_columns,
+`bitwise_table` over ms_bitwise_table and `bitwise_multiplicities` over ms_bitwise_multiplicities (include/ministark_hip_bitwise.h):
+c = a AND / OR / XOR b on the canonical integers of two columns, the table (op, x, y, x op y) over all pairs of `bits`-bit limbs written on
+the device, and that table's multiplicities counted straight from the word columns a, b, c -- the limb pairs are taken from registers."""
 import ctypes
 
 import numpy as np
 
-from ._lib import (GapColumnRecord, GapReportRecord, GapSpecRecord, JoinReportRecord, LimbReportRecord, LimbSpecRecord, LookupReportRecord, LookupTupleRecord,
+from ._lib import (BitwiseSetRecord, BitwiseSpecRecord, GapColumnRecord, GapReportRecord, GapSpecRecord, JoinReportRecord, LimbReportRecord, LimbSpecRecord, LookupReportRecord, LookupTupleRecord,
                    RangeSetRecord, SortKeyRecord, SortReportRecord)
 from .api import FIELD_WORDS, GOLDILOCKS_FP, STARK252_FP, DeviceBytes, GpuVec, Matrix, _ptr_array, f252_from_mont_limbs, gl_from_mont
 
@@ -50,6 +55,9 @@ LOOKUP_MAX_WIDTH, LOOKUP_MAX_SETS = 4, 8
 SORT_MAX_KEYS, PERMUTE_MAX_COLUMNS = 4, 128
 JOIN_MAX_WIDTH, JOIN_MAX_SETS, JOIN_NONE = 4, 8, 0xFFFFFFFF
 RANGE_MAX_SPECS, RANGE_MAX_SETS, RANGE_MAX_LIMBS, RANGE_MAX_LIMB_BITS, RANGE_MAX_TABLE_BITS = 64, 64, 256, 32, 24
+BITWISE_MAX_SPECS, BITWISE_MAX_SETS, BITWISE_MAX_LIMBS, BITWISE_MAX_BITS, BITWISE_MAX_OPS, BITWISE_MAX_TABLE_LOG = 64, 64, 256, 12, 3, 24
+BITWISE_OPS = {"and": 0, "or": 1, "xor": 2}                      # MS_BIT_AND, MS_BIT_OR, MS_BIT_XOR
+BITWISE_WMAX = {GOLDILOCKS_FP: 63, STARK252_FP: 251}             # 2^WMAX is the widest power of two below the modulus
 
 
 def _mask_words(who, mask):
@@ -642,6 +650,207 @@ def range_multiplicities(planner, trace, bits, sets, out=None, n_m=None):
     L.check(L.ms_range_multiplicities(planner.handle, field, n, _ptr_array(cols), len(cols), bits, rec.ctypes.data if rec.size else None, len(sets),
                                       n_m, m.ptr, buf.ptr))
     return m, RangeReport(planner, buf, cols, sets, bits)
+
+
+def _bitwise_op(who, op):
+    """"and" | "or" | "xor" | 0 | 1 | 2 -> the op code"""
+    code = BITWISE_OPS.get(op, op) if isinstance(op, str) else op
+    if code not in (0, 1, 2):
+        raise ValueError(f"{who}: op is 'and', 'or' or 'xor' (0, 1, 2), not {op!r}")
+    return int(code)
+
+
+def bitwise_apply(op, x, y):
+    """x op y on Python integers, op a code or a name"""
+    code = _bitwise_op("bitwise_apply", op)
+    return x & y if code == 0 else x | y if code == 1 else x ^ y
+
+
+class BitwiseSpec:
+    """One result column: base column `dst` = (a mod 2^width) op (b mod 2^width) on the canonical integers of base columns `a` and `b`
+    (a == b is allowed); op "and", "or", "xor".  mask: None, ("nonzero", m) or ("zero", m), as for ExtColumn: an inactive row gets zero."""
+
+    def __init__(self, op, a, b, dst, width, mask=None):
+        self.op, self.a, self.b, self.dst, self.width, self.mask = _bitwise_op("BitwiseSpec", op), int(a), int(b), int(dst), int(width), mask
+        if not 1 <= self.width <= max(BITWISE_WMAX.values()):
+            raise ValueError(f"BitwiseSpec: an operand has 1 .. {max(BITWISE_WMAX.values())} bits, not {self.width}")
+        _mask_words("BitwiseSpec", mask)
+
+    def _record(self):
+        """the eight 32-bit words of ms_bitwise_spec: op, a, b, dst, width, mask, mask_col, pad"""
+        mask = _mask_words("BitwiseSpec", self.mask)
+        return [self.op, self.a, self.b, self.dst, self.width, mask[0], mask[1], 0]
+
+
+class BitwiseSet:
+    """One looked-up operation of a bitwise check: the `nlimbs` limb pairs of base columns `a` and `b` under `op`, and the result column `c`
+    to check against a op b (None: there is none).  mask as for ExtColumn."""
+
+    def __init__(self, op, a, b, c, nlimbs, mask=None):
+        self.op, self.a, self.b, self.c, self.nlimbs, self.mask = _bitwise_op("BitwiseSet", op), int(a), int(b), None if c is None else int(c), int(nlimbs), mask
+        if self.c is not None and self.c < 0:
+            raise ValueError(f"BitwiseSet: c is a column index or None, not {c}")
+        if not 1 <= self.nlimbs <= BITWISE_MAX_LIMBS:
+            raise ValueError(f"BitwiseSet: 1 .. {BITWISE_MAX_LIMBS} limbs, not {self.nlimbs}")
+        self.cols = [self.a, self.b] + ([] if self.c is None else [self.c])
+        _mask_words("BitwiseSet", mask)
+
+    def _record(self):
+        """the eight 32-bit words of ms_bitwise_set: op, a, b, c, nlimbs, mask, mask_col, pad"""
+        mask = _mask_words("BitwiseSet", self.mask)
+        return [self.op, self.a, self.b, -1 if self.c is None else self.c, self.nlimbs, mask[0], mask[1], 0]
+
+
+class BitwiseColumnsReport(LimbReport):
+    """What `bitwise_columns` found: a LimbReport whose overflow counts the active rows with an operand that does not fit `width` bits."""
+
+    def first_overflow_value(self):
+        """the canonical values (a, b) of the first overflowing row (it downloads those two elements, nothing else), or None"""
+        if not self.overflow:
+            return None
+        spec, row = self._specs[self.first_overflow_spec], self.first_overflow_row
+        return (_canonical_at(self.planner, self._cols[spec.a], row), _canonical_at(self.planner, self._cols[spec.b], row))
+
+    def check(self):
+        """raises LookupMissing, naming spec, row and both operands, when an operand does not fit its width"""
+        if self.overflow:
+            k, row, v = self.first_overflow_spec, self.first_overflow_row, self.first_overflow_value()
+            spec = self._specs[k]
+            err = LookupMissing(f"bitwise spec {k}, row {row}: the operands {v[0]} and {v[1]} in base columns {spec.a} and {spec.b} do not both fit {spec.width} bits; "
+                                f"{self.overflow} row(s) in all do not fit")
+            err.set, err.spec, err.row, err.values, err.missing = k, k, row, list(v), self.overflow
+            raise err
+        return self
+
+
+class BitwiseReport(LookupReport):
+    """What `bitwise_multiplicities` found: a LookupReport (duplicate_table_rows is 0) whose check() names the set, the row and the three
+    canonical values a, b, c of the first row that is not in the table: an operand past its limbs, or c != a op b."""
+
+    def __init__(self, planner, buf, cols, sets, bits):
+        super().__init__(planner, buf, cols, sets)
+        self.bits = bits
+
+    def __repr__(self):
+        return f"BitwiseReport(missing={self.missing}, first_missing_set={self.first_missing_set}, first_missing_row={self.first_missing_row})"
+
+    def first_missing_values(self):
+        """[a, b, c] of the first missing row as canonical integers (it downloads those elements, nothing else), c = a op b where the set
+        has no result column; or None"""
+        vals = super().first_missing_values()
+        if vals is not None and len(vals) == 2:
+            vals.append(bitwise_apply(self._lookups[self.first_missing_set].op, vals[0], vals[1]))
+        return vals
+
+    def check(self):
+        if self.missing:
+            s, row, vals = self.first_missing_set, self.first_missing_row, self.first_missing_values()
+            st = self._lookups[s]
+            name = {v: k for k, v in BITWISE_OPS.items()}[st.op]
+            err = LookupMissing(f"bitwise set {s}, row {row}: a = {vals[0]}, b = {vals[1]}, c = {vals[2]} in base columns {st.a}, {st.b}, {st.c}: an operand is not below "
+                                f"2^{st.nlimbs * self.bits} ({st.nlimbs} limbs of {self.bits} bits) or c is not a {name} b; {self.missing} looked-up row(s) in all are not in the table")
+            err.set, err.row, err.values, err.missing = s, row, vals, self.missing
+            raise err
+        return self
+
+
+def bitwise_columns(planner, trace, specs):
+    """Writes the result column of every BitwiseSpec into `trace` (a Matrix or a list of GpuVecs of one length and field) -> a LimbReport
+    (its overflow: active rows with an operand that does not fit `width` bits; their low bits still go into the result).  The dst of a spec
+    is a column of the trace that no spec reads (as operand or mask) and no other spec writes.  Enqueues and returns: no host wait until the
+    report is read."""
+    cols = trace.columns if isinstance(trace, Matrix) else list(trace)
+    specs = list(specs)
+    n, field = _same_columns("bitwise_columns", cols)
+    if field not in BITWISE_WMAX:
+        raise ValueError("bitwise_columns: the trace is over Fp or Fp252")
+    if len(specs) > BITWISE_MAX_SPECS:
+        raise ValueError(f"bitwise_columns: at most {BITWISE_MAX_SPECS} specs in one call, not {len(specs)}")
+    for k, sp in enumerate(specs):
+        if sp.width > BITWISE_WMAX[field]:
+            raise ValueError(f"bitwise_columns: spec {k}: an operand of this field has 1 .. {BITWISE_WMAX[field]} bits, not {sp.width}")
+    buf = GpuVec(planner, ctypes.sizeof(LimbReportRecord) // 8, GOLDILOCKS_FP)
+    rec = np.array([sp._record() for sp in specs], dtype=np.int32).reshape(-1, 8)
+    assert rec.nbytes == len(specs) * ctypes.sizeof(BitwiseSpecRecord)
+    L = planner.lib
+    L.check(L.ms_bitwise_columns(planner.handle, field, n, _ptr_array(cols), len(cols), rec.ctypes.data if rec.size else None, len(specs), buf.ptr))
+    return BitwiseColumnsReport(planner, buf, cols, specs)
+
+
+def _bitwise_ops(who, bits, ops):
+    bits, codes = int(bits), [_bitwise_op(who, op) for op in ops]
+    if not 1 <= bits <= BITWISE_MAX_BITS:
+        raise ValueError(f"{who}: bits is 1 .. {BITWISE_MAX_BITS}, not {bits}")
+    if not 1 <= len(codes) <= BITWISE_MAX_OPS or len(set(codes)) != len(codes):
+        raise ValueError(f"{who}: 1 .. {BITWISE_MAX_OPS} distinct ops, not {list(ops)!r}")
+    T = len(codes) << (2 * bits)
+    if T > 1 << BITWISE_MAX_TABLE_LOG:
+        raise ValueError(f"{who}: {len(codes)} ops over pairs of {bits}-bit limbs are {T} table rows (at most 2^{BITWISE_MAX_TABLE_LOG})")
+    return bits, np.array(codes, dtype=np.int32), T
+
+
+def bitwise_table(planner, field, bits, ops, n_t=None, out=None, with_op=None):
+    """-> [top, tx, ty, tz] (top is None without an op column): the table (op, x, y, x op y) over all pairs of `bits`-bit limbs, op by op in
+    the order of `ops`, x the slower index, padded to n_t rows (default: the table's own len(ops) * 4^bits) by repeating the last row.
+    out: the four GpuVecs to fill, [top or None, tx, ty, tz], or None for new ones; with_op: write the op column (default: when there is
+    more than one op).  Enqueues and returns."""
+    bits, codes, T = _bitwise_ops("bitwise_table", bits, ops)
+    if field not in BITWISE_WMAX:
+        raise ValueError("bitwise_table: the table is over Fp or Fp252")
+    if out is not None:
+        out = list(out)
+        if len(out) != 4 or any(c is None for c in out[1:]):
+            raise ValueError("bitwise_table: out is [top or None, tx, ty, tz]")
+    if n_t is None:
+        n_t = min(len(c) for c in out if c is not None) if out is not None else T
+    n_t = int(n_t)
+    if n_t < T:
+        raise ValueError(f"bitwise_table: the columns hold {n_t} elements, fewer than the {T} rows of the table")
+    if out is None:
+        with_op = len(codes) > 1 if with_op is None else with_op
+        out = [GpuVec(planner, n_t, field) if with_op else None] + [GpuVec(planner, n_t, field) for _ in range(3)]
+    if any(c is not None and (len(c) < n_t or c.field != field) for c in out):
+        raise ValueError("bitwise_table: `out` holds columns of `field` of at least n_t elements")
+    L = planner.lib
+    L.check(L.ms_bitwise_table(planner.handle, field, bits, codes.ctypes.data, len(codes), n_t, out[0].ptr if out[0] is not None else None, out[1].ptr, out[2].ptr, out[3].ptr))
+    return out
+
+
+def bitwise_multiplicities(planner, trace, bits, ops, sets, out=None, n_m=None):
+    """-> (m, report): m[slot * 4^bits + (x << bits) + y] = how many limb pairs (x, y) the active, valid rows of the `sets` (BitwiseSet
+    records) of the op at position `slot` of `ops` hold, and zero from len(ops) * 4^bits to n_m (default: the length of `out`, or of the
+    trace), as elements of the base field -- the multiplicities of `bitwise_table`'s rows.  out: the GpuVec to fill (its first n_m elements)
+    -- it may be a column of `trace` that no set and no mask names -- or None for a new one.  report: a BitwiseReport; a row with an
+    operand not below 2^(nlimbs * bits), or whose c is not a op b, is counted there as missing and none of its limbs is counted.
+    Enqueues and returns: no host wait until it is read."""
+    cols = trace.columns if isinstance(trace, Matrix) else list(trace)
+    sets = list(sets)
+    n, field = _same_columns("bitwise_multiplicities", cols)
+    bits, codes, T = _bitwise_ops("bitwise_multiplicities", bits, ops)
+    if field not in BITWISE_WMAX:
+        raise ValueError("bitwise_multiplicities: the trace is over Fp or Fp252")
+    if len(sets) > BITWISE_MAX_SETS:
+        raise ValueError(f"bitwise_multiplicities: at most {BITWISE_MAX_SETS} sets in one call, not {len(sets)}")
+    for s, st in enumerate(sets):
+        if st.op not in codes:
+            raise ValueError(f"bitwise_multiplicities: set {s}: its op is not one of the table's ops")
+        if st.nlimbs * bits > BITWISE_WMAX[field]:
+            raise ValueError(f"bitwise_multiplicities: set {s}: {st.nlimbs} limbs of {bits} bits are more than the {BITWISE_WMAX[field]} bits an operand may have")
+    if n_m is None:
+        n_m = len(out) if out is not None else n
+    n_m = int(n_m)
+    if n_m < T:
+        raise ValueError(f"bitwise_multiplicities: m holds {n_m} elements, fewer than the {T} rows of the table")
+    m = GpuVec(planner, n_m, field) if out is None else out
+    if len(m) < n_m or m.field != field:
+        raise ValueError("bitwise_multiplicities: `out` is a column of the base field of at least n_m elements")
+    buf = GpuVec(planner, ctypes.sizeof(LookupReportRecord) // 8, GOLDILOCKS_FP)
+    rec = np.array([s._record() for s in sets], dtype=np.int32).reshape(-1, 8)
+    assert rec.nbytes == len(sets) * ctypes.sizeof(BitwiseSetRecord)
+    L = planner.lib
+    L.check(L.ms_bitwise_multiplicities(planner.handle, field, n, _ptr_array(cols), len(cols), bits, codes.ctypes.data, len(codes),
+                                        rec.ctypes.data if rec.size else None, len(sets), n_m, m.ptr, buf.ptr))
+    return m, BitwiseReport(planner, buf, cols, sets, bits)
 
 
 GAP_MAX_GROUP, GAP_MAX_COLUMNS = 3, 128

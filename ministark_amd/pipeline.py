@@ -358,6 +358,87 @@ def range_air(n, bits):
     return comp, ce, ncoeffs, 1, columns
 
 
+_BITWISE = {"and": (0, lambda x, y: x & y), "or": (1, lambda x, y: x | y), "xor": (2, lambda x, y: x ^ y)}
+BITWISE_COLUMNS = ("a", "b", "c", "a0", "a1", "b0", "b1", "c0", "c1", "tx", "ty", "tz", "m")
+
+
+def bitwise_trace(n, bits, op, seed):
+    """A valid base trace of `bitwise_air`: columns a, b, c, a0, a1, b0, b1, c0, c1, tx, ty, tz, m as canonical integers.  a and b are
+    drawn below 2^(2 bits), c = a op b (op "and", "or" or "xor"), x0 and x1 are the low and high limbs of `bits` bits of x, (tx, ty, tz) is
+    the table (x, y, x op y) over all pairs of limbs -- row x * 2^bits + y -- padded to n rows by repeating its last row, and m[j] counts
+    how often table row j is the limb triple (a_k, b_k, c_k) of a row, k = 0, 1 (zero from 4^bits on).  n >= 4^bits."""
+    assert 1 <= bits <= 8 and n >= (1 << (2 * bits)) and op in _BITWISE
+    fn, lm, T = _BITWISE[op][1], (1 << bits) - 1, 1 << (2 * bits)
+    rng = np.random.default_rng(seed)
+    a = [int(v) for v in rng.integers(0, T, size=n, dtype=np.uint64)]
+    b = [int(v) for v in rng.integers(0, T, size=n, dtype=np.uint64)]
+    c = [fn(x, y) for x, y in zip(a, b)]
+    limbs = [[v & lm for v in col] if k == 0 else [v >> bits for v in col] for col in (a, b, c) for k in (0, 1)]
+    rows = [min(j, T - 1) for j in range(n)]
+    tx, ty = [r >> bits for r in rows], [r & lm for r in rows]
+    m = [0] * n
+    for k in (0, 1):
+        for x, y in zip(limbs[k], limbs[2 + k]):
+            m[(x << bits) + y] += 1
+    return [a, b, c] + limbs + [tx, ty, [fn(x, y) for x, y in zip(tx, ty)], m]
+
+
+def bitwise_trace_on_device(planner, n, bits, op, seed, check=False, a=None, b=None, c=None):
+    """`bitwise_trace(n, bits, op, seed)` built where the trace lies: a and b are uploaded beside eleven zero columns, ms_bitwise_columns
+    (extension.bitwise_columns) writes c, one ms_limb_decompose writes the six limb columns, ms_bitwise_table writes tx, ty, tz and
+    ms_bitwise_multiplicities counts the limb pairs of (a, b), checked against c, into m in place -- from the word columns: the limb columns
+    are columns of the AIR, not inputs of the count.  Nothing is downloaded.
+    -> the base trace as a Matrix of thirteen Fp columns, equal to the uploaded `bitwise_trace` in every word.  check: read the three
+    reports (host waits) and raise LookupMissing if an operand does not fit two limbs or c is not a op b.
+    a, b: the operands, in place of the drawn ones (canonical integers).  c: a result column uploaded in place of the one
+    ms_bitwise_columns would write -- the negative control of a prover that got it wrong."""
+    from .extension import BitwiseSet, BitwiseSpec, LimbSpec, bitwise_columns, bitwise_multiplicities, bitwise_table, limb_decompose
+    cols = bitwise_trace(n, bits, op, seed)
+    words = lambda c: to_mont_words(GOLDILOCKS_FP, c).ravel()
+    zero = np.zeros(n, dtype=np.uint64)
+    trace = Matrix.from_numpy(planner, [words(cols[0] if a is None else a), words(cols[1] if b is None else b), zero if c is None else words(c)] + [zero] * 10, GOLDILOCKS_FP)
+    made = bitwise_columns(planner, trace, [BitwiseSpec(op, 0, 1, 2, 2 * bits)] if c is None else [])
+    limbs = limb_decompose(planner, trace, [LimbSpec(src, 3 + 2 * src, 2, bits) for src in range(3)])
+    bitwise_table(planner, GOLDILOCKS_FP, bits, [op], n_t=n, out=[None] + trace.columns[9:12])
+    _, counts = bitwise_multiplicities(planner, trace, bits, [op], [BitwiseSet(op, 0, 1, 2, 2)], out=trace.columns[12])
+    if check:
+        made.check()
+        limbs.check()
+        counts.check()
+    return trace
+
+
+def bitwise_air_constraints(n, bits):
+    """The five constraints of `bitwise_air`, in its order: the recompositions x = x0 + 2^bits x1 of a, b and c on every row, the boundary
+    S = 0 at row 0, and the LogUp transition, the transitions over the full zerofier X^n - 1."""
+    x = E.X()
+    cur, nxt, ch = (lambda k: E.Trace(k, 0)), (lambda k: E.Trace(k, 1)), E.Challenge
+    S = 13
+    zerofier = x ** n - E.Constant(1)
+    den = lambda cx, cy, cz: ch(0) - cur(cx) - ch(1) * cur(cy) - ch(2) * cur(cz)
+    dt, d0, d1 = den(9, 10, 11), den(3, 5, 7), den(4, 6, 8)
+    return [(cur(src) - cur(3 + 2 * src) - E.Constant(1 << bits) * cur(4 + 2 * src)) / zerofier for src in range(3)] + [
+            cur(S) / (x - E.Constant(1)),
+            ((nxt(S) - cur(S)) * dt * d0 * d1 - cur(12) * d0 * d1 + dt * d1 + dt * d0) / zerofier]
+
+
+def bitwise_air(n, bits, op):
+    """An AIR of a bitwise operation, valid on `bitwise_trace`: a, b and c are two limbs of `bits` bits each, and both limb triples
+    (a_k, b_k, c_k) are rows of the table (tx, ty, tz) = (x, y, x op y), which is looked up m times.  Base columns 0..12 = a, b, c, a0, a1,
+    b0, b1, c0, c1, tx, ty, tz, m; extension column 13 = S; challenges 0, 1, 2 = alpha, beta1, beta2:
+        x - x0 - 2^bits x1 = 0  for x = a, b, c
+        S' = S + m / (alpha - tx - beta1 ty - beta2 tz) - sum_k 1 / (alpha - a_k - beta1 b_k - beta2 c_k)
+    S = 0 at row 0, and the transition, cleared of its three denominators, on EVERY row (divided by X^n - 1), as in `range_air`: degree 4,
+    ce_blowup 4.  `op` is in the table column tz alone: the constraints are the same for the three ops.
+    -> (composition constraint, ce_blowup, number of composition coefficients, number of AIR challenges 3, the LogUpColumn record)."""
+    from .extension import LogUpColumn
+    assert op in _BITWISE
+    comp, ce, ncoeffs = composition_constraint(n, bitwise_air_constraints(n, bits), num_air_challenges=3)
+    den = lambda cx, cy, cz: [(+1, 0, None), (-1, None, cx), (-1, 1, cy), (-1, 2, cz)]
+    columns = [LogUpColumn(0, [([(+1, None, 12)], den(9, 10, 11)), ([(-1, None, None)], den(3, 5, 7)), ([(-1, None, None)], den(4, 6, 8))])]
+    return comp, ce, ncoeffs, 3, columns
+
+
 def memory_processor_rows(steps, seed):
     """The processor table of a small tape machine, as canonical integers: columns cycle, mp, mem_val, instr; `steps` executed rows and the
     final state row, whose instr is 0.  Instructions 1..4, drawn at random: increment and decrement the cell under the pointer (mod p), move

@@ -20,6 +20,7 @@
 pub mod plan;
 pub mod stage;
 pub mod sys;
+pub mod sys_bitwise;
 pub mod sys_blake3;
 pub mod sys_keccak;
 pub mod sys_ext;

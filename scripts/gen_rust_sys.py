@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generate rust/gpu/src/hip/sys.rs -- the raw `extern "C"` bindings of the reference-side shim -- from
-include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h, sys_gaps.rs from include/ministark_hip_gaps.h, sys_join.rs from include/ministark_hip_join.h, sys_poseidon.rs from include/ministark_hip_poseidon.h, sys_hades_coin.rs from include/ministark_hip_hades_coin.h sys_blake3.rs from include/ministark_hip_blake3.h and sys_range.rs from include/ministark_hip_range.h.  tests/test_rust_shim.py re-runs the parser and
+include/ministark_hip.h, one Rust declaration per C prototype, sys_transcript.rs from include/ministark_hip_transcript.h, sys_keccak.rs from include/ministark_hip_keccak.h sys_ext.rs from include/ministark_hip_ext.h and sys_logup.rs from include/ministark_hip_logup.h, sys_rpo_coin.rs from include/ministark_hip_rpo_coin.h, sys_lookup.rs from include/ministark_hip_lookup.h, sys_sort.rs from include/ministark_hip_sort.h, sys_gaps.rs from include/ministark_hip_gaps.h, sys_join.rs from include/ministark_hip_join.h, sys_poseidon.rs from include/ministark_hip_poseidon.h, sys_hades_coin.rs from include/ministark_hip_hades_coin.h sys_blake3.rs from include/ministark_hip_blake3.h, sys_range.rs from include/ministark_hip_range.h and sys_bitwise.rs from include/ministark_hip_bitwise.h.  tests/test_rust_shim.py re-runs the parser and
 checks the committed file against the header, which stands in for compiling it (no Rust toolchain in the image).
 
     python scripts/gen_rust_sys.py            # rewrite rust/gpu/src/hip/sys.rs
@@ -38,6 +38,8 @@ BLAKE3_HEADER = os.path.join(ROOT, "include", "ministark_hip_blake3.h")
 BLAKE3_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_blake3.rs")
 RANGE_HEADER = os.path.join(ROOT, "include", "ministark_hip_range.h")
 RANGE_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_range.rs")
+BITWISE_HEADER = os.path.join(ROOT, "include", "ministark_hip_bitwise.h")
+BITWISE_OUT = os.path.join(ROOT, "rust", "gpu", "src", "hip", "sys_bitwise.rs")
 
 BASE = {"int": "c_int", "unsigned": "c_uint", "unsigned int": "c_uint", "long": "c_long", "size_t": "usize", "uint64_t": "u64",
         "uint32_t": "u32", "char": "c_char", "unsigned char": "u8", "void": "c_void", "ms_ctx": "ms_ctx", "ms_ntt_plan": "ms_ntt_plan", "ms_xchg_op": "ms_xchg_op", "ms_p2p_op": "ms_p2p_op", "ms_jit_stats": "ms_jit_stats"}
@@ -470,6 +472,32 @@ def range_prototypes():
     return prototypes(text[text.index("#define MINISTARK_HIP_RANGE_H"):])
 
 
+def render_bitwise(protos):
+    """sys_bitwise.rs: the entry points of include/ministark_hip_bitwise.h (bitwise-operation columns, their table and its direct-indexed
+    multiplicities), on sys.rs's types; the reports are sys_range.rs's ms_limb_report and sys_lookup.rs's ms_lookup_report"""
+    lines = ["// GENERATED by scripts/gen_rust_sys.py from include/ministark_hip_bitwise.h -- do not edit by hand.",
+             "// Raw bindings of the bitwise-operation layer of libministark_hip.so (INTEGRATION.md section 3e); ms_limb_report: sys_range.rs; ms_lookup_report: sys_lookup.rs; the MS_EXT_* mask kinds: sys_ext.rs.",
+             "#![allow(non_camel_case_types)]",
+             "use core::ffi::{c_int, c_uint, c_void};",
+             "use super::sys::ms_ctx;",
+             "",
+             "#[repr(C)] #[derive(Clone, Copy, Debug, Default)] pub struct ms_bitwise_spec { pub op: i32, pub a: i32, pub b: i32, pub dst: i32, pub width: i32, pub mask: i32, pub mask_col: i32, pub pad: i32 }",
+             "#[repr(C)] #[derive(Clone, Copy, Debug, Default)] pub struct ms_bitwise_set { pub op: i32, pub a: i32, pub b: i32, pub c: i32, pub nlimbs: i32, pub mask: i32, pub mask_col: i32, pub pad: i32 }",
+             ] + [f"pub const {name}: c_int = {value};" for name, value in header_enums(BITWISE_HEADER)] + [
+             "",
+             '#[link(name = "ministark_hip")]', 'extern "C" {']
+    for name, ret, plist in protos:
+        args = ", ".join(f"{(p + '_') if p in RUST_KEYWORDS else p}: {t}" for p, t in plist)
+        lines.append(f"    pub fn {name}({args})" + (f" -> {ret};" if ret else ";"))
+    lines += ["}", ""]
+    return "\n".join(lines)
+
+
+def bitwise_prototypes():
+    text = open(BITWISE_HEADER).read()
+    return prototypes(text[text.index("#define MINISTARK_HIP_BITWISE_H"):])
+
+
 def main():
     protos = prototypes(open(HEADER).read())
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
@@ -528,6 +556,10 @@ def main():
     with open(RANGE_OUT, "w") as f:
         f.write(render_range(protos))
     print(f"{len(protos)} prototypes -> {RANGE_OUT}")
+    protos = bitwise_prototypes()
+    with open(BITWISE_OUT, "w") as f:
+        f.write(render_bitwise(protos))
+    print(f"{len(protos)} prototypes -> {BITWISE_OUT}")
 
 
 if __name__ == "__main__":
