@@ -121,6 +121,7 @@ __device__ __forceinline__ void net1(uint64_t* x, const Params& P, unsigned b, c
 template <bool STREAM, bool UNI, int V = 1, bool REV = false>      // REV: the column backwards (Params::rev), an inverse transform's pass A
 __global__ void __launch_bounds__(NT, 4) lde2_strided_pass(Params P) {
     static_assert(!REV || V == 1, "the backwards read is an Fp plan");
+    constexpr int SIDES = msntt2::POL_NT;                   // NTT2_LD / NTT2_ST: a STREAM launch hints both sides
     __shared__ uint64_t xch[16 * 8 * TW];                    // 64 KiB: [b][a' - 8 round][lane]
     const uint64_t* __restrict__ src = P.src[blockIdx.z];
     // Which (tile, coset) this workgroup takes.  A tile of coefficients is read by all beta cosets; in plain grid order (tile fastest) the
@@ -231,6 +232,7 @@ static constexpr int X2P = 65;                               // pitch of the sec
 // workgroup produces meet in its LDS and leave as whole runs of 48 T consecutive words: no partial line is ever stored.
 template <bool STREAM, int T, bool UNI, bool NATURAL = false, int V = 1, int OSCALE = 0>     // OSCALE (NATURAL): 1 the constant, 2 the table of Params
 __global__ void __launch_bounds__(NT, 4) lde2_rows_pass(Params P) {
+    constexpr int SIDES = msntt2::POL_NT;                   // NTT2_LD / NTT2_ST: a STREAM launch hints both sides
     static_assert(OSCALE == 0 || NATURAL, "the output scale of an inverse transform belongs to the natural-order stores");
     static_assert(!NATURAL || T <= 4, "natural-order stores: runs of 64 / T words, T = 2 or 4");
     static_assert(V == 1 || (V == 3 && T <= 16 && !NATURAL), "Fq3 columns: rows of at most 4096 elements, bit-reversed order");

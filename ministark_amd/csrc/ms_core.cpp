@@ -69,6 +69,19 @@ int ctx_scratch(ms_ctx* ctx, size_t bytes, void** out) {
     return MS_OK;
 }
 
+int ctx_side_streams(ms_ctx* ctx, unsigned count) {
+    if (count > (unsigned)MAX_CHAINS - 1) return fail(MS_ERR_INVALID, "internal: %u side streams", count);
+    if (!ctx->ev_fork) HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+    for (unsigned i = 0; i < count; i++) {
+        if (!ctx->side[i]) HIPCHK(hipStreamCreateWithFlags(&ctx->side[i], hipStreamNonBlocking));
+        if (!ctx->ev_join[i]) HIPCHK(hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming));
+    }
+    return MS_OK;
+}
+void ctx_side_sync(ms_ctx* ctx) {
+    for (hipStream_t s : ctx->side) if (s) (void)hipStreamSynchronize(s);
+}
+
 extern "C" int ms_ctx_create(int device, ms_ctx** out) {
     if (!out) return fail(MS_ERR_INVALID, "ms_ctx_create: out is null");
     int count = 0;
@@ -89,7 +102,7 @@ extern "C" int ms_comm_destroy(ms_ctx* ctx);
 extern "C" int ms_ctx_destroy(ms_ctx* ctx) {
     if (!ctx) return MS_OK;
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
+    ctx_side_sync(ctx);
     (void)ms_comm_destroy(ctx);
     plans_release_ctx(ctx);                                    // handles the caller still holds (they refer to this context)
     for (auto& kv : ctx->plan_cache) plan_free_cached(kv.second);
@@ -99,7 +112,11 @@ extern "C" int ms_ctx_destroy(ms_ctx* ctx) {
     if (ctx->stage) (void)hipHostFree(ctx->stage);
     { std::lock_guard<std::mutex> lk(ctx->land_mu); if (ctx->land) (void)hipHostFree(ctx->land); ctx->land = nullptr; }
     for (auto m : ctx->jit_modules) (void)hipModuleUnload(m);
-    if (ctx->stream2) { (void)hipStreamDestroy(ctx->stream2); (void)hipEventDestroy(ctx->ev_fork); (void)hipEventDestroy(ctx->ev_join); }
+    for (int i = 0; i < MAX_CHAINS - 1; i++) {
+        if (ctx->side[i]) (void)hipStreamDestroy(ctx->side[i]);
+        if (ctx->ev_join[i]) (void)hipEventDestroy(ctx->ev_join[i]);
+    }
+    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return MS_OK;

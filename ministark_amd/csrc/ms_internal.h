@@ -63,13 +63,16 @@ struct JitStats { uint64_t compiled = 0, from_disk = 0, failures = 0, damaged_en
 JitStats& jit_process_stats();              // the process-wide totals (ms_eval_jit_check has no context)
 
 struct ms_ntt_plan;
+static constexpr int MAX_CHAINS = 4;
 struct PlanKey { unsigned V, log_n; bool inverse; uint64_t h; };
 struct ms_ctx {
     int device = 0;
     std::vector<std::pair<PlanKey, ms_ntt_plan*>> plan_cache;   // plans used by the fused entry points
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;            // second half of a column group in plan_run (created on first use)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // side streams of run_passes, between a fork and a join event each (ctx_side_streams creates them on first use): the second half of a
+    // column group under MS_NTT_STREAMS=2, chains 1 .. S-1 of the column chains.  MAX_CHAINS streams with ctx->stream: the runtime's queue limit
+    hipStream_t side[MAX_CHAINS - 1] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[MAX_CHAINS - 1] = {};
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
     // columns are processed in groups of about this size (= the scratch buffer).  Measured at 2^24: one column per
@@ -130,6 +133,8 @@ struct ProfScope {
 
 
 int ctx_scratch(ms_ctx* ctx, size_t bytes, void** out);
+int ctx_side_streams(ms_ctx* ctx, unsigned count);                // side[0 .. count) and their events exist afterwards; the caller holds ctx->mu
+void ctx_side_sync(ms_ctx* ctx);                                  // waits for whatever the side streams still hold
 int pool_alloc(ms_ctx* ctx, size_t bytes, void** d_ptr);          // the caller holds ctx->mu
 int pool_free(ms_ctx* ctx, void* d_ptr);
 int stage_upload(ms_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);   // the caller holds ctx->mu; h_src may be reused at once

@@ -7,6 +7,9 @@
 #include "stage_kernels.h"
 #include "scan_kernels.h"
 
+// The column chains' defaults (profiles/ntt_column_chains.txt): on or off, streams, smallest column (log2 points)
+static constexpr bool CHAIN_DEFAULT_ON = true;
+static constexpr unsigned CHAIN_STREAMS = 2, CHAIN_MIN_LOG = 23;
 // The switches read once per process, at the first transform.
 struct NttSwitches {
     // MS_NTT_FUSED_SMALL=0: 2^11 .. 2^14-point Fp columns take the launches they took before ntt_fused_tiny / ntt_fused_small (before / after timings)
@@ -22,6 +25,12 @@ struct NttSwitches {
     // Columns below 2^20 points lose with it (round 4, MS_NTT_STREAMS_MIN_LOG=12: 2^16 x 128 0.67 -> 0.88 us per column, 2^17 x 64 1.40 -> 1.60).
     bool two_streams = getenv("MS_NTT_STREAMS") != nullptr && atoi(getenv("MS_NTT_STREAMS")) == 2;
     unsigned two_min_log = getenv("MS_NTT_STREAMS_MIN_LOG") ? (unsigned)atoi(getenv("MS_NTT_STREAMS_MIN_LOG")) : 20u;
+    // MS_NTT_CHAINS: the column chains of run_passes (CHAIN_DEFAULT_ON decides without it: =0 the batch launches, =1 the chains);
+    // MS_NTT_CHAIN_STREAMS (1 .. 4, never more: the runtime's queue limit) and MS_NTT_CHAIN_MIN_LOG override the number of streams and the
+    // smallest column (log2 points) that takes the route -- for measurements and tests
+    bool chains = getenv("MS_NTT_CHAINS") ? !strcmp(getenv("MS_NTT_CHAINS"), "1") : CHAIN_DEFAULT_ON;
+    unsigned chain_streams = getenv("MS_NTT_CHAIN_STREAMS") ? (unsigned)std::min(std::max(atoi(getenv("MS_NTT_CHAIN_STREAMS")), 1), MAX_CHAINS) : CHAIN_STREAMS;
+    unsigned chain_min_log = getenv("MS_NTT_CHAIN_MIN_LOG") ? (unsigned)atoi(getenv("MS_NTT_CHAIN_MIN_LOG")) : CHAIN_MIN_LOG;
     // MS_LDE2_FQ3=0: Fq3 columns off the two-pass coset LDE (before / after timings, tests of the three-pass route); =all: from 2^17 rows
     // on (the tests reach the T = 2 instantiation)
     bool fq3_off = getenv("MS_LDE2_FQ3") && !strcmp(getenv("MS_LDE2_FQ3"), "0");
@@ -138,6 +147,26 @@ template <bool S> static K2 limb_pass_kernel(const ms_ntt_plan* p, int q, int na
     return last_pass_kernel<S>(p->inverse, p->scale_mode, bitrev_out);
 }
 
+// ... under cache policy `pol` (ntt2_kernels.h).  Both sides hinted or neither: every pass of every limb-form plan (the batch launches).  One side:
+// what the column chains launch -- loads-only the first pass, stores-only the last natural-order pass, of Fp columns of a uniform-factor plan
+static K2 limb_pass_kernel(int pol, const ms_ntt_plan* p, int q, int na, bool small_mid, bool perm, bool bitrev_out) {
+    using namespace msntt2;
+    switch (pol) {
+    case POL_PLAIN: return limb_pass_kernel<false>(p, q, na, small_mid, perm, bitrev_out);
+    case POL_NT: return limb_pass_kernel<true>(p, q, na, small_mid, perm, bitrev_out);
+    case POL_NT_LD:
+        if (q != 0 || !perm || na != 16) return nullptr;
+        if (p->inverse) return ntt2_first_pass<true, true, false, 16, true, true, POL_NT_LD>;
+        return p->coset ? ntt2_first_pass<true, false, true, 16, true, true, POL_NT_LD> : ntt2_first_pass<true, false, false, 16, true, true, POL_NT_LD>;
+    case POL_NT_ST:
+        if (q != p->npass - 1 || q == 0 || small_mid || bitrev_out) return nullptr;
+        if (!p->inverse) return ntt2_mid_pass<true, false, true, 0, false, false, POL_NT_ST>;
+        return p->scale_mode == 2 ? ntt2_mid_pass<true, true, true, 2, false, false, POL_NT_ST>
+             : p->scale_mode == 1 ? ntt2_mid_pass<true, true, true, 1, false, false, POL_NT_ST> : ntt2_mid_pass<true, true, true, 0, false, false, POL_NT_ST>;
+    default: return nullptr;
+    }
+}
+
 // the two-pass coset LDE (lde2_kernels.h).  Pass A: Fq3 columns (V = 3) without the uniform split (T = 2) have the streaming variant alone;
 // rev: the column backwards, an inverse transform's pass A (Fp, uniform split)
 static KLde lde2_pass_a_kernel(bool stream, bool uni, unsigned V, bool rev) {
@@ -239,9 +268,6 @@ static int run_inverse_2_18(ms_ntt_plan* p, ms_ntt_plan* fwd1, const void* const
     return lde2_run(fwd1, 18, 0, src, dst, ncols, true, 1, owner);
 }
 
-// The pass loop: 2 .. 4 passes through a scratch column, each the limb-form kernel (ntt2_kernels.h) where the pass has one, the round-1
-// kernel (ntt_kernels.h) otherwise.  valid_rows < 256: pass 1 reads only the first valid_rows/256 of the source; bitrev_out: the last
-// pass stores in bit-reversed order.
 template <class Params>
 static void pass_columns(Params& P, int q, bool last, const void* const* src, void* const* dst, void* scratch, size_t col_bytes, unsigned c0, unsigned nc) {
     for (unsigned c = 0; c < nc; c++) {
@@ -250,90 +276,153 @@ static void pass_columns(Params& P, int q, bool last, const void* const* src, vo
         P.dst[c] = last ? (uint64_t*)dst[c0 + c] : scr;
     }
 }
+// one call of run_passes: what every launch of it shares
+struct PassRun {
+    ms_ntt_plan* p;
+    const void* const* src;
+    void* const* dst;
+    unsigned valid_rows;
+    bool bitrev_out;
+    size_t n, col_bytes;
+    bool perm;      // uniform-factor plans on Fp columns: pass 1 stores whole lines in a row order that permutes the words inside every run of
+                    // 64; pass 2 un-permutes while it reads, in place on the scratch column (its tile owns those 64 words), and the last pass
+                    // goes scratch -> dst (natural order, or bit-reversed for the LDE)
+    int na;         // sixteenths of pass 1's rows that hold data
+};
+static bool small_mid_pass(const ms_ntt_plan* p, int q) { return p->uni && q == 1 && p->lr[q] < 8; }
+// limb-form radix-256 passes (ntt2_kernels.h) wherever a pass has radix 256 and rows of >= 64 words
+// (the per-element scale walk of an inverse coset transform stays with the round-1 last pass: the walk is two table
+// loads and a Montgomery product per word, which the 4-wave limb kernel hides worse -- 91 vs 75 us per 2^24
+// column; so does the fused bit-reversed store of Fq3 columns, whose runs interleave three words)
+static bool limb_pass_ok(const PassRun& R, int q) {
+    const ms_ntt_plan* p = R.p;
+    const bool last = (q == p->npass - 1);
+    const size_t pass_sw = ((size_t)1 << p->log_s[q]) * p->V;
+    return small_mid_pass(p, q) || (p->lr[q] == 8 && (R.n * p->V) % msntt2::TILE == 0 &&
+           (q == 0 ? ((R.n >> 8) * p->V) % msntt2::TW == 0
+                   : (pass_sw % msntt2::TW == 0 && !(last && p->scale_mode == 2 && p->d_scu4 == nullptr) &&
+                      !(last && R.bitrev_out && (p->V != 1 || p->inverse || p->scale_mode != 0)))));
+}
+// Pass q of columns [c0, c0 + nc) on stream st: source -> scratch, scratch in place, scratch -> destination; column c of the range
+// goes through scratch column c.  pol: the cache policy of a limb-form pass's tile accesses (ntt2_kernels.h).
+static int launch_pass(const PassRun& R, int q, hipStream_t st, unsigned c0, unsigned nc, void* scratch, int pol) {
+    ms_ntt_plan* p = R.p;
+    ms_ctx* ctx = p->ctx;
+    const size_t n = R.n;
+    const bool last = (q == p->npass - 1);
+    static const char* const pass_names[4] = {"ntt_pass1", "ntt_pass2", "ntt_pass3", "ntt_pass4"};
+    ProfScope ps(ctx, pass_names[q], 2.0 * R.col_bytes * nc);
+    const bool small_mid = small_mid_pass(p, q);
+    const bool v2_ok = limb_pass_ok(R, q);
+    if (switches().debug) fprintf(stderr, "[ms_ntt] log_n=%u V=%u pass %d/%d radix 2^%u: %s kernel\n", p->log_n, p->V, q + 1, p->npass, p->lr[q], v2_ok ? (p->uni && q < 2 ? "limb-form (ntt2), uniform inter-pass factor" : "limb-form (ntt2)") : "round-1");
+    if (p->uni && q < 2 && !v2_ok) return fail(MS_ERR_INVALID, "internal: uniform inter-pass plan without its limb-form passes");
+    if (v2_ok) {
+        msntt2::Params Q;
+        memset(&Q, 0, sizeof Q);
+        pass_columns(Q, q, last, R.src, R.dst, scratch, R.col_bytes, c0, nc);
+        Q.wr4 = p->d_wr4[q]; Q.twu4 = p->d_twu4[q]; Q.sc4 = p->d_sc4; Q.scu4 = p->d_scu4; Q.g4 = p->d_g4;
+        Q.tw_lo = p->d_tw_lo; Q.tw_hi = p->d_tw_hi; Q.aux_lo = p->d_aux_lo; Q.aux_hi = p->d_aux_hi;
+        Q.log_n = p->log_n; Q.V = p->V; Q.valid_rows = R.valid_rows; Q.lo_bits = p->lo_bits; Q.log_s = p->log_s[q];
+        Q.tin4 = p->d_tin4; Q.tout4 = p->d_tout4; Q.lq = p->d_lq; Q.r3 = p->lr[2];
+        // pass 1 of a uniform-factor plan with last radix 256 (four tiles per block of a row): XCD-aware tile order (ntt2_kernels.h)
+        Q.xcd_map = (q == 0 && p->uni && p->V == 1 && p->lr[2] == 8 && (n / msntt2::TILE) % 8 == 0) ? 1u : 0u;
+        Q.nfields = p->nfields[q];
+        for (unsigned f = 0; f < Q.nfields; f++) Q.fields[f] = p->fields[q][f];
+        const K2 k = limb_pass_kernel(pol, p, q, R.na, small_mid, R.perm, R.bitrev_out);
+        if (!k) return fail(MS_ERR_INVALID, "internal: no limb-form kernel of pass %d under cache policy %d", q + 1, pol);
+        hipLaunchKernelGGL(k, dim3((unsigned)(n * p->V / msntt2::TILE), nc), dim3(msntt2::NT), 0, st, Q);
+        return MS_OK;
+    }
+    msntt::PassParams P;
+    memset(&P, 0, sizeof P);
+    pass_columns(P, q, last, R.src, R.dst, scratch, R.col_bytes, c0, nc);
+    P.tw_lo = p->d_tw_lo; P.tw_hi = p->d_tw_hi; P.wr = p->d_wr[q];
+    P.aux_lo = p->d_aux_lo; P.aux_hi = p->d_aux_hi; P.gtab = p->d_gtab;
+    P.log_n = p->log_n; P.V = p->V; P.valid_rows = R.valid_rows; P.lo_bits = p->lo_bits; P.log_s = p->log_s[q];
+    P.nfields = p->nfields[q];
+    for (unsigned f = 0; f < P.nfields; f++) P.fields[f] = p->fields[q][f];
+    P.scale_const = p->scale_const;
+    const K1 k = q == 0 ? first_pass_r1(p->inverse, !p->inverse && p->coset, R.na) : mid_pass_r1(p->lr[q], p->inverse, last, p->scale_mode, R.bitrev_out);
+    if (!k) return fail(MS_ERR_INVALID, "internal: bad pass radix 2^%u", p->lr[q]);
+    hipLaunchKernelGGL(k, dim3((unsigned)(n * p->V / msntt::TILE), nc), dim3(msntt::NT), 0, st, P);
+    return MS_OK;
+}
+// side streams 0 .. count-1 start where the context's stream stands / the context's stream goes on when they are done
+static int fork_side_streams(ms_ctx* ctx, unsigned count) {
+    MSCHK(ctx_side_streams(ctx, count));
+    HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
+    for (unsigned i = 0; i < count; i++) HIPCHK(hipStreamWaitEvent(ctx->side[i], ctx->ev_fork, 0));
+    return MS_OK;
+}
+static int join_side_streams(ms_ctx* ctx, unsigned count) {
+    for (unsigned i = 0; i < count; i++) {
+        HIPCHK(hipEventRecord(ctx->ev_join[i], ctx->side[i]));
+        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join[i], 0));
+    }
+    return MS_OK;
+}
+
+// The column chains (profiles/ntt_column_chains.txt).  In batch order a pass covers every column of the group, so pass k + 1 reads a line
+// a whole group of traffic after pass k wrote it and every one of the six trips over a column reaches HBM.  Here the columns are dealt
+// round-robin to S streams; a stream owns ONE scratch column and runs pass 1 -> 2 -> 3 of its columns one after the other, so the
+// intermediate column (written twice, read twice) stays in the 256 MiB Infinity Cache.  Only the side of a pass that touches the column
+// itself carries the non-temporal hint.  Ordering is stream order plus the fork and join events: no waiting on the device, the same
+// kernels on the same words as the batch.
+static bool chains_apply(const PassRun& R, unsigned ncols) {
+    const NttSwitches& sw = switches();
+    const ms_ntt_plan* p = R.p;
+    if (!sw.chains || sw.two_streams || p->ctx->profiling || ncols < 2) return false;      // (profiling: events on one stream, one launch per pass)
+    if (!p->uni || p->V != 1 || p->npass != 3 || R.valid_rows != 256 || R.bitrev_out || p->log_n < sw.chain_min_log) return false;
+    if (2 * R.col_bytes > ((size_t)256 << 20)) return false;                                // a column and a scratch column fit the cache
+    return limb_pass_ok(R, 0) && limb_pass_ok(R, 1) && limb_pass_ok(R, 2);
+}
+static int run_chains(const PassRun& R, unsigned ncols) {
+    ms_ctx* ctx = R.p->ctx;
+    const unsigned S = std::min(switches().chain_streams, ncols);
+    void* scratch = nullptr;
+    MSCHK(ctx_scratch(ctx, (size_t)S * R.col_bytes, &scratch));
+    if (switches().debug) fprintf(stderr, "[ms_ntt] log_n=%u: %u columns as chains on %u streams\n", R.p->log_n, ncols, S);
+    MSCHK(fork_side_streams(ctx, S - 1));
+    static const int policy[3] = {msntt2::POL_NT_LD, msntt2::POL_PLAIN, msntt2::POL_NT_ST};     // pass 2 works on the scratch column alone (hinted stores: slower)
+    for (unsigned c = 0; c < ncols; c++) {
+        const unsigned s = c % S;
+        const hipStream_t st = s == 0 ? ctx->stream : ctx->side[s - 1];
+        for (int q = 0; q < 3; q++) MSCHK(launch_pass(R, q, st, c, 1, (char*)scratch + (size_t)s * R.col_bytes, policy[q]));
+    }
+    MSCHK(join_side_streams(ctx, S - 1));
+    HIPCHK(hipGetLastError());
+    return MS_OK;
+}
+
+// The pass loop: 2 .. 4 passes through a scratch column, each the limb-form kernel (ntt2_kernels.h) where the pass has one, the round-1
+// kernel (ntt_kernels.h) otherwise.  valid_rows < 256: pass 1 reads only the first valid_rows/256 of the source; bitrev_out: the last
+// pass stores in bit-reversed order.
 static int run_passes(ms_ntt_plan* p, const void* const* src, void* const* dst, unsigned ncols, unsigned valid_rows, bool bitrev_out) {
     ms_ctx* ctx = p->ctx;
     const NttSwitches& sw = switches();
-    const size_t n = (size_t)1 << p->log_n;
-    const size_t col_bytes = n * p->V * 8;
+    PassRun R{p, src, dst, valid_rows, bitrev_out, (size_t)1 << p->log_n, ((size_t)1 << p->log_n) * p->V * 8, p->uni && p->V == 1,
+              valid_rows == 64 ? 4 : valid_rows == 32 ? 2 : valid_rows == 16 ? 1 : 16};
+    if (chains_apply(R, ncols)) return run_chains(R, ncols);
+    const size_t col_bytes = R.col_bytes;
     unsigned group = (unsigned)std::max<size_t>(1, std::min<size_t>(MAXC, ctx->group_bytes / col_bytes));
     group = std::min(group, ncols);
-    // uniform-factor plans on Fp columns: pass 1 stores whole lines in a row order that permutes the words inside every run of
-    // 64; pass 2 un-permutes while it reads, in place on the scratch column (its tile owns those 64 words), and the last pass
-    // goes scratch -> dst (natural order, or bit-reversed for the LDE).
-    const bool perm = p->uni && p->V == 1;
-    const int na = valid_rows == 64 ? 4 : valid_rows == 32 ? 2 : valid_rows == 16 ? 1 : 16;
     void* scratch_all = nullptr;
     MSCHK(ctx_scratch(ctx, (size_t)group * col_bytes, &scratch_all));
     // the two-stream split (NttSwitches::two_streams): the halves of a group between a fork and a join event
     const bool two = sw.two_streams && !ctx->profiling && ncols >= 2 && group >= 2 && p->log_n >= sw.two_min_log;
-    if (two) {
-        if (!ctx->stream2) {
-            HIPCHK(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-        }
-        HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
-        HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-    }
+    if (two) MSCHK(fork_side_streams(ctx, 1));
     for (unsigned g0 = 0; g0 < ncols; g0 += group) {
       const unsigned gnc = std::min(group, ncols - g0);
       const unsigned half = (two && gnc >= 2) ? gnc / 2 : gnc;
       for (unsigned s0 = 0; s0 < gnc; s0 = (s0 == 0) ? half : gnc) {     // at most two ranges: [0, half), [half, gnc)
         const unsigned c0 = g0 + s0, nc = (s0 == 0) ? half : gnc - half;
-        const hipStream_t st = (s0 == 0) ? ctx->stream : ctx->stream2;
+        const hipStream_t st = (s0 == 0) ? ctx->stream : ctx->side[0];
         void* const scratch = (char*)scratch_all + (size_t)s0 * col_bytes;
-        for (int q = 0; q < p->npass; q++) {
-            const bool last = (q == p->npass - 1);
-            static const char* const pass_names[4] = {"ntt_pass1", "ntt_pass2", "ntt_pass3", "ntt_pass4"};
-            ProfScope ps(ctx, pass_names[q], 2.0 * col_bytes * nc);
-            // limb-form radix-256 passes (ntt2_kernels.h) wherever a pass has radix 256 and rows of >= 64 words
-            const size_t pass_sw = ((size_t)1 << p->log_s[q]) * p->V;
-            // (the per-element scale walk of an inverse coset transform stays with the round-1 last pass: the walk is two table
-            // loads and a Montgomery product per word, which the 4-wave limb kernel hides worse -- 91 vs 75 us per 2^24
-            // column; so does the fused bit-reversed store of Fq3 columns, whose runs interleave three words)
-            const bool small_mid = p->uni && q == 1 && p->lr[q] < 8;
-            const bool v2_ok = small_mid || (p->lr[q] == 8 && (n * p->V) % msntt2::TILE == 0 &&
-                               (q == 0 ? ((n >> 8) * p->V) % msntt2::TW == 0
-                                       : (pass_sw % msntt2::TW == 0 && !(last && p->scale_mode == 2 && p->d_scu4 == nullptr) &&
-                                          !(last && bitrev_out && (p->V != 1 || p->inverse || p->scale_mode != 0)))));
-            if (sw.debug) fprintf(stderr, "[ms_ntt] log_n=%u V=%u pass %d/%d radix 2^%u: %s kernel\n", p->log_n, p->V, q + 1, p->npass, p->lr[q], v2_ok ? (p->uni && q < 2 ? "limb-form (ntt2), uniform inter-pass factor" : "limb-form (ntt2)") : "round-1");
-            if (p->uni && q < 2 && !v2_ok) return fail(MS_ERR_INVALID, "internal: uniform inter-pass plan without its limb-form passes");
-            if (v2_ok) {
-                msntt2::Params Q;
-                memset(&Q, 0, sizeof Q);
-                pass_columns(Q, q, last, src, dst, scratch, col_bytes, c0, nc);
-                Q.wr4 = p->d_wr4[q]; Q.twu4 = p->d_twu4[q]; Q.sc4 = p->d_sc4; Q.scu4 = p->d_scu4; Q.g4 = p->d_g4;
-                Q.tw_lo = p->d_tw_lo; Q.tw_hi = p->d_tw_hi; Q.aux_lo = p->d_aux_lo; Q.aux_hi = p->d_aux_hi;
-                Q.log_n = p->log_n; Q.V = p->V; Q.valid_rows = valid_rows; Q.lo_bits = p->lo_bits; Q.log_s = p->log_s[q];
-                Q.tin4 = p->d_tin4; Q.tout4 = p->d_tout4; Q.lq = p->d_lq; Q.r3 = p->lr[2];
-                // pass 1 of a uniform-factor plan with last radix 256 (four tiles per block of a row): XCD-aware tile order (ntt2_kernels.h)
-                Q.xcd_map = (q == 0 && p->uni && p->V == 1 && p->lr[2] == 8 && (n / msntt2::TILE) % 8 == 0) ? 1u : 0u;
-                Q.nfields = p->nfields[q];
-                for (unsigned f = 0; f < Q.nfields; f++) Q.fields[f] = p->fields[q][f];
-                const K2 k = beyond_cache(nc, col_bytes) ? limb_pass_kernel<true>(p, q, na, small_mid, perm, bitrev_out)
-                                                         : limb_pass_kernel<false>(p, q, na, small_mid, perm, bitrev_out);
-                hipLaunchKernelGGL(k, dim3((unsigned)(n * p->V / msntt2::TILE), nc), dim3(msntt2::NT), 0, st, Q);
-                continue;
-            }
-            msntt::PassParams P;
-            memset(&P, 0, sizeof P);
-            pass_columns(P, q, last, src, dst, scratch, col_bytes, c0, nc);
-            P.tw_lo = p->d_tw_lo; P.tw_hi = p->d_tw_hi; P.wr = p->d_wr[q];
-            P.aux_lo = p->d_aux_lo; P.aux_hi = p->d_aux_hi; P.gtab = p->d_gtab;
-            P.log_n = p->log_n; P.V = p->V; P.valid_rows = valid_rows; P.lo_bits = p->lo_bits; P.log_s = p->log_s[q];
-            P.nfields = p->nfields[q];
-            for (unsigned f = 0; f < P.nfields; f++) P.fields[f] = p->fields[q][f];
-            P.scale_const = p->scale_const;
-            const K1 k = q == 0 ? first_pass_r1(p->inverse, !p->inverse && p->coset, na) : mid_pass_r1(p->lr[q], p->inverse, last, p->scale_mode, bitrev_out);
-            if (!k) return fail(MS_ERR_INVALID, "internal: bad pass radix 2^%u", p->lr[q]);
-            hipLaunchKernelGGL(k, dim3((unsigned)(n * p->V / msntt::TILE), nc), dim3(msntt::NT), 0, st, P);
-        }
+        for (int q = 0; q < p->npass; q++)
+            MSCHK(launch_pass(R, q, st, c0, nc, scratch, beyond_cache(nc, col_bytes) ? msntt2::POL_NT : msntt2::POL_PLAIN));
       }
     }
-    if (two) {
-        HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-    }
+    if (two) MSCHK(join_side_streams(ctx, 1));
     HIPCHK(hipGetLastError());
     return MS_OK;
 }

@@ -100,7 +100,7 @@ static int plan_free(ms_ntt_plan* plan) {
         return MS_OK;
     }
     (void)hipStreamSynchronize(plan->ctx->stream);
-    if (plan->ctx->stream2) (void)hipStreamSynchronize(plan->ctx->stream2);
+    ctx_side_sync(plan->ctx);
     if (plan->d_tables) (void)hipFree(plan->d_tables);
     if (plan->d_oscale) (void)hipFree(plan->d_oscale);
     for (auto& l : plan->lde2) if (l.d) (void)hipFree(l.d);

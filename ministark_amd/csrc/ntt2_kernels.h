@@ -53,12 +53,16 @@ template <class T> MS_HD void nt_store(T* p, const T& v) { *p = v; }
 namespace msntt2 { using gld::lane_xor1; }      // gl_dev.h: the word of the neighbouring lane (one DPP move per half)
 // STREAM is the kernels' first template parameter: the launcher sets it when data + scratch of a launch exceed the 256 MiB Infinity
 // Cache (ms_ntt.cpp).  Batches that fit stay on the default policy: the next pass finds them in the cache, and the hint costs
-// 2^17 x 64 columns 1.37 -> 1.54 us per column (profiles/r04_c2_sweep_nt_always.json).
+// 2^17 x 64 columns 1.37 -> 1.54 us per column (profiles/r04_c2_sweep_nt_always.json).  SIDES, their last one, says which side of a
+// STREAM launch carries the hint: the tile loads, the tile stores, or both (the default).  The column chains (ms_ntt.cpp: run_chains) hint
+// only the side of a pass that touches the column itself, so that the scratch column of a chain stays in the cache from one pass to the
+// next.  Together they are the cache policy of a launch, one bit per side: POL_PLAIN = !STREAM, POL_NT_LD / POL_NT_ST / POL_NT = SIDES.
+namespace msntt2 { enum : int { POL_PLAIN = 0, POL_NT_LD = 1, POL_NT_ST = 2, POL_NT = 3 }; }
 #ifndef NTT2_LD
-#define NTT2_LD(p, pass) (STREAM ? msntt2::nt_load(p) : *(p))
+#define NTT2_LD(p, pass) ((STREAM && (SIDES & msntt2::POL_NT_LD)) ? msntt2::nt_load(p) : *(p))
 #endif
 #ifndef NTT2_ST
-#define NTT2_ST(p, v, pass) do { if constexpr (STREAM) msntt2::nt_store(p, v); else *(p) = (v); } while (0)
+#define NTT2_ST(p, v, pass) do { if constexpr (STREAM && (SIDES & msntt2::POL_NT_ST) != 0) msntt2::nt_store(p, v); else *(p) = (v); } while (0)
 #endif
 
 namespace msntt2 {
@@ -282,7 +286,7 @@ __device__ __forceinline__ void net1(uint64_t* x, const Params& P, unsigned b, c
 //   a permutation INSIDE each run of 64 words.  The 64 words k1 = 64 q + lane of this tile are therefore this tile's own four
 //   128-byte lines, read once in a permuted lane order; the stores go to the natural positions, so the permutation ends here
 //   and the pass may run in place (every word of the tile is read before the first one is stored).
-template <bool STREAM, bool INV, bool LAST, int SCALE, bool LOADQ = false, bool PERM = false>
+template <bool STREAM, bool INV, bool LAST, int SCALE, bool LOADQ = false, bool PERM = false, int SIDES = POL_NT>
 __global__ void __launch_bounds__(NT, 4) ntt2_mid_pass(Params P) {
     __shared__ uint64_t xch[16 * 8 * TW];                    // 64 KiB: [b][a' - 8 round][lane]
     const uint64_t* __restrict__ src = P.src[blockIdx.y];
@@ -398,7 +402,7 @@ __global__ void __launch_bounds__(NT, 4) ntt2_mid_pass(Params P) {
 // (LOADQ's per-lane factor, see ntt2_mid_pass), the network, and the wave-uniform factor w_U^k2 (twu4[U][k2], with h^j3 of a
 // coset transform) on the stores.  A workgroup takes 256 / R runs (32 words per lane, 16384 per workgroup, as everywhere).
 // PERM: the rows are in the order ntt2_first_pass<.., PERM> leaves them; the natural order is restored here, in place.
-template <bool STREAM, bool INV, int LOGR, bool PERM>
+template <bool STREAM, bool INV, int LOGR, bool PERM, int SIDES = POL_NT>
 __global__ void __launch_bounds__(NT, 4) ntt2_small_mid_pass(Params P) {
     constexpr int R = 1 << LOGR, NNET = 32 / R;               // networks per lane
     const uint64_t* __restrict__ src = P.src[blockIdx.y];
@@ -469,7 +473,7 @@ __global__ void __launch_bounds__(NT, 4) ntt2_small_mid_pass(Params P) {
 // per-lane factor on the loads), times w_R^(a' b) (wave-uniform: wr4 holds the powers of w_R for this pass), exchange through LDS in which every word
 // stays in its lane and slot (s, c) collects the outputs a' = c mod T2 of all b, radix-T2 networks over b, times the
 // wave-uniform w_U^k2 (twu4[U][k2], k2 = a' + 16 b') on the stores.  PERM as in ntt2_mid_pass (in place).
-template <bool STREAM, bool INV, int LOGT2, bool PERM>
+template <bool STREAM, bool INV, int LOGT2, bool PERM, int SIDES = POL_NT>
 __global__ void __launch_bounds__(NT, 4) ntt2_mid_pass_r(Params P) {
     constexpr int T2 = 1 << LOGT2, R = 16 * T2, NM = 8 / T2;  // NM networks of radix T2 per slot and round
     static_assert(LOGT2 >= 1 && LOGT2 <= 3, "R = 32, 64 or 128");
@@ -570,7 +574,7 @@ __global__ void __launch_bounds__(NT, 4) ntt2_mid_pass_r(Params P) {
 // store one whole 128-byte line.  The buffer is shared with the exchange, so here the second half of the first networks'
 // results waits in registers until round 0 has stored (a few spilled registers, as before round 2b).
 static constexpr int BR_PITCH = 129;
-template <bool STREAM>
+template <bool STREAM, int SIDES = POL_NT>
 __global__ void __launch_bounds__(NT, 4) ntt2_last_pass_bitrev(Params P) {
     __shared__ uint64_t xch[64 * BR_PITCH];                  // >= 16 * 8 * TW words of the exchange
     const uint64_t* __restrict__ src = P.src[blockIdx.y];
@@ -655,7 +659,7 @@ __device__ __forceinline__ unsigned first_pass_tile(unsigned b, unsigned ntiles)
     const unsigned x = b & 7, i = b >> 3, g = x & 3, j2 = (x >> 2) * (ntiles >> 3) + i;
     return j2 * 4 + g;
 }
-template <bool STREAM, bool INV, bool COSET, int NA, bool UNI = false, bool PERM = false>
+template <bool STREAM, bool INV, bool COSET, int NA, bool UNI = false, bool PERM = false, int SIDES = POL_NT>
 __global__ void __launch_bounds__(NT, 4) ntt2_first_pass(Params P) {
     __shared__ uint64_t xch[16 * 8 * XPITCH];                // [b][a' - 8 round][word], pitch 68 words
     const uint64_t* __restrict__ src = P.src[blockIdx.y];

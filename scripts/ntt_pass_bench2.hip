@@ -1,6 +1,9 @@
 // Round 4: the three kernels of the 2^24 forward coset transform (and the transform in batch order) under compile-time variants of
 // ntt2_kernels.h: -DVAR_NTL (non-temporal tile loads), -DVAR_NTS (non-temporal tile stores), -DVAR_HOT (every workgroup on tiles 0..3:
 // arithmetic + exchange + issue alone), -DVAR_... added as they are tried.  Tables hold arbitrary residues (timing only).
+// After the batch: the transform as chains per column (pass 1 -> 2 -> 3 of a column through one scratch column) on the null stream, on 1 / 2 / 4
+// forked streams, and the same with four calls between the events (profiles/ntt_column_chains.txt: -DVAR_NTL=7 -DVAR_NTS=7 is the batch of the
+// library, -DVAR_NTL=1 -DVAR_NTS=4 the chains' hints, -DVAR_XCD pass 1's tile order).  argv: tag, rounds.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I ministark_amd/csrc [-DVAR_x] scripts/ntt_pass_bench2.hip -o scripts/ntt_pass_bench2_x
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -93,7 +96,8 @@ int main(int argc, char** argv) {
     };
     for (int i = 0; i < 400; i++) pass(1, 0, 0, NC);      // settle the clocks
     CK(hipDeviceSynchronize());
-    for (int round = 0; round < 3; round++) {
+    const int rounds = argc > 2 ? atoi(argv[2]) : 3;
+    for (int round = 0; round < rounds; round++) {
         const double t1 = time_us([&] { pass(0, 0, 0, NC); }) / NC, t2 = time_us([&] { pass(1, 0, 0, NC); }) / NC, t3 = time_us([&] { pass(2, 0, 0, NC); }) / NC;
         const double tt = time_us([&] { pass(0, 0, 0, NC); pass(1, 0, 0, NC); pass(2, 0, 0, NC); }) / NC;
         printf("%-10s pass 1 %6.1f  pass 2 %6.1f  pass 3 %6.1f  sum %6.1f   transform (batch order) %6.1f us/column = %.3f of 8 TB/s\n",
@@ -101,18 +105,27 @@ int main(int argc, char** argv) {
         // chain per column through ONE scratch column (128 MiB: stays in the Infinity Cache), one stream; and two chains on two streams
         scr_of = 0;
         const double tc = time_us([&] { for (unsigned c = 0; c < NC; c++) { pass(0, 0, c, 1); pass(1, 0, c, 1); pass(2, 0, c, 1); } }) / NC;
-        static hipStream_t s2[2] = {nullptr, nullptr};
-        static hipEvent_t ev[3];
-        if (!s2[0]) { for (int i = 0; i < 2; i++) CK(hipStreamCreateWithFlags(&s2[i], hipStreamNonBlocking)); for (int i = 0; i < 3; i++) CK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)); }
-        const double tc2 = time_us([&] {
-            CK(hipEventRecord(ev[2], 0));
-            for (int i = 0; i < 2; i++) CK(hipStreamWaitEvent(s2[i], ev[2], 0));
-            for (unsigned c = 0; c < NC; c++) { scr_of = c & 1; pass(0, s2[c & 1], c, 1); pass(1, s2[c & 1], c, 1); pass(2, s2[c & 1], c, 1); }
-            for (int i = 0; i < 2; i++) { CK(hipEventRecord(ev[i], s2[i])); CK(hipStreamWaitEvent(0, ev[i], 0)); }
-        }) / NC;
+        // S chains on S streams between a fork and a join event, columns dealt round-robin, one scratch column per stream
+        static hipStream_t s2[4] = {nullptr, nullptr, nullptr, nullptr};
+        static hipEvent_t ev[5];
+        if (!s2[0]) { for (int i = 0; i < 4; i++) CK(hipStreamCreateWithFlags(&s2[i], hipStreamNonBlocking)); for (int i = 0; i < 5; i++) CK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)); }
+        auto chains = [&](unsigned S) {
+            CK(hipEventRecord(ev[4], 0));
+            for (unsigned i = 0; i < S; i++) CK(hipStreamWaitEvent(s2[i], ev[4], 0));
+            for (unsigned c = 0; c < NC; c++) { scr_of = c % S; pass(0, s2[c % S], c, 1); pass(1, s2[c % S], c, 1); pass(2, s2[c % S], c, 1); }
+            for (unsigned i = 0; i < S; i++) { CK(hipEventRecord(ev[i], s2[i])); CK(hipStreamWaitEvent(0, ev[i], 0)); }
+        };
+        double tcs[3];
+        for (int si = 0; si < 3; si++) tcs[si] = time_us([&] { chains(1u << si); }) / NC;
+        // the same with four calls between the events, the way a caller that does not wait between calls (bench.py) sees them: the host's part
+        // of the 24 launches and of the fork and the join is hidden behind the call before
+        double tq[3];
+        for (int si = 0; si < 3; si++) tq[si] = time_us([&] { for (int k = 0; k < 4; k++) chains(1u << si); }) / NC / 4;
         scr_of = 0xFFFFFFFFu;
-        printf("%-10s chain per column, one scratch column: %6.1f us/column = %.3f;  two chains on two streams (two scratch columns): %6.1f = %.3f\n",
-               tag, tc, 268435456.0 / (tc * 1e-6) / 8e12, tc2, 268435456.0 / (tc2 * 1e-6) / 8e12);
+        const double tbq = time_us([&] { for (int k = 0; k < 4; k++) { pass(0, 0, 0, NC); pass(1, 0, 0, NC); pass(2, 0, 0, NC); } }) / NC / 4;
+        printf("%-10s four calls back to back: batch %6.1f   forked chains: 1 stream %6.1f  2 streams %6.1f  4 streams %6.1f\n", tag, tbq, tq[0], tq[1], tq[2]);
+        printf("%-10s chain per column, one scratch column: %6.1f us/column = %.3f;  forked chains, one scratch column per stream: 1 stream %6.1f  2 streams %6.1f  4 streams %6.1f\n",
+               tag, tc, 268435456.0 / (tc * 1e-6) / 8e12, tcs[0], tcs[1], tcs[2]);
         fflush(stdout);
     }
     return 0;
