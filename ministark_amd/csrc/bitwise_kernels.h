@@ -3,14 +3,14 @@
 //   bitwise_columns    grid (blocks, specs), grid-stride, one lane per row: the canonical words of both operands once (Canon<V>::words),
 //                      cut to `width` bits, combined word by word, back to Montgomery form, one coalesced store.  The next row's words are
 //                      loaded before this row's store goes out.  A lane counts its active and its overflowing rows; a workgroup adds its
-//                      sums once (msrg::block_totals).
+//                      sums once (mstab::block_totals).
 //   bitwise_col_finish one lane: the report.
-//   bitwise_table      grid-stride, one lane per table row: op, x, y, x op y as field elements (all below 2^12: msrg::limb_elem).
+//   bitwise_table      grid-stride, one lane per table row: op, x, y, x op y as field elements (all below 2^12: msdc::limb_elem).
 //   bitwise_count_plain  grid (blocks, sets), grid-stride, one lane per row: nlimbs adds cnt[slot * 4^bits + (x_j << bits) + y_j] += 1 in
 //                      global memory through mslk::count_found, which adds once for the lanes of a wave that hit the wave's first bin.
 //                      Correct for every `bits`.
 //   bitwise_count_lds  grid (G, nops): workgroup (g, slot) takes its share of the rows of every set whose op has that slot and keeps the
-//                      slot's 4^bits bins as a histogram of its own in LDS, then one global add per non-zero bin (msrg::flush_bins).
+//                      slot's 4^bits bins as a histogram of its own in LDS, then one global add per non-zero bin (msdc::flush_bins).
 //                      HB <= 15: 2^HB 32-bit counters, which cannot overflow (the increments of a call are below 2^32).  HB = 16: 2^16 16-bit
 //                      counters, two to a word.  A row adds nlimbs increments, all of which may fall on one bin, so the flush interval is
 //                      counted in INCREMENTS per lane: at most FLUSH_INCS * LNT <= 65 535 between two flushes, and the low half never
@@ -19,21 +19,18 @@
 //   bitwise_finish     grid-stride: counter -> field element -> d_m, zero past the table; lane 0 writes the report.
 // An operand is in range when it is below 2^(nlimbs bits) AS AN INTEGER; a result column is right when every word of it is.
 // Integer adds and mins commute: counters and reports are the same on every run.  Every atomic is table_common.h's (plain
-// read-modify-write under MS_EMU).  Canon, above, limb_elem, block_totals and flush_bins are range_kernels.h's, included as they are.
+// read-modify-write under MS_EMU).  above, limb_elem, the histogram, the writer's parameter record and its report are direct_count.h's,
+// which brings lookup_kernels.h (count_found, from_count, Report, EMPTY); Canon and block_totals are table_common.h's.
 #pragma once
-// range_kernels.h was written for one unit: its limb_finish is a kernel that is no template, with external linkage.  This unit includes
-// the header as it is and takes that one kernel under a name of its own (never launched), so that the two units link.
-#define limb_finish limb_finish_of_bitwise_unit
-#include "range_kernels.h"
-#undef limb_finish
+#include "direct_count.h"
 
 namespace msbw {
 
-static constexpr int NT = msrg::NT, LNT = msrg::LNT, MAXSPECS = 64, MAXSETS = 64, MAXOPS = 3;
+static constexpr int NT = msdc::NT, LNT = msdc::LNT, MAXSPECS = 64, MAXSETS = 64, MAXOPS = 3;
 static constexpr int OP_AND = 0, OP_OR = 1, OP_XOR = 2;
 static constexpr int PACKED_BITS = 8;                     // the limb width whose pair table has 2^16 bins: the packed form
 static constexpr int PACKED_MAX_LIMBS = 251 / PACKED_BITS;   // the most limbs a row can have there (Fp252; Fp has 63 / 8)
-static constexpr int FLUSH_INCS = 63;                     // 63 * 1024 = 64 512 increments between two flushes of the packed counters
+static constexpr int FLUSH_INCS = msdc::FLUSH_ADDS;       // a row is nlimbs adds: the increments of a lane between two flushes of the packed counters
 static_assert(FLUSH_INCS * LNT <= 65535, "a 16-bit counter must not wrap between two flushes: the bound is in increments, not rows");
 static_assert(PACKED_MAX_LIMBS <= FLUSH_INCS, "one row's increments must fit between two flushes");
 
@@ -51,15 +48,7 @@ struct Spec {
     uint32_t dst, width, op;
     int32_t mask_kind;
 };
-struct ColParams {
-    const Spec* specs;                        // [gridDim.y], device memory
-    uint64_t* const* base;                    // the caller's pointer table, device memory
-    uint64_t* overflow;                       // zero before bitwise_columns
-    uint64_t* active;                         // zero
-    uint64_t* first;                          // min over the overflowing rows of (spec << 32 | row); all ones
-    msrg::LimbReport* report;
-    size_t n;
-};
+using ColParams = msdc::WriterParams<Spec>;
 
 template <int V> struct Pair { uint64_t a[V], b[V]; bool active; };
 
@@ -93,18 +82,15 @@ __global__ void __launch_bounds__(NT) bitwise_columns(ColParams P) {
     const Spec S = P.specs[blockIdx.y];
     uint64_t* dst = P.base[S.dst];
     const size_t stride = (size_t)gridDim.x * NT;
-    uint64_t nactive = 0, noverflow = 0, first = ~0ull;
+    uint64_t nactive = 0, noverflow = 0;
+    mstab::FirstRow first{~0ull};
     size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
     Pair<V> cur = load_pair<V>(S, i, P.n);
     while (i < P.n) {
         const Pair<V> next = load_pair<V>(S, i + stride, P.n);               // in flight while this row's result goes out
         if (cur.active) {
             nactive++;
-            if (msrg::above<V>(cur.a, S.width) || msrg::above<V>(cur.b, S.width)) {
-                noverflow++;
-                const uint64_t at = (uint64_t)blockIdx.y << 32 | (uint64_t)i;
-                if (at < first) first = at;
-            }
+            if (msdc::above<V>(cur.a, S.width) || msdc::above<V>(cur.b, S.width)) { noverflow++; first.see(blockIdx.y, i); }
         }
         uint64_t r[V];                                                         // an inactive row's words are zero, and so is 0 op 0
         #pragma unroll
@@ -113,19 +99,10 @@ __global__ void __launch_bounds__(NT) bitwise_columns(ColParams P) {
         cur = next;
         i += stride;
     }
-    msrg::block_totals(nactive, noverflow, first, P.active, P.overflow, P.first);
+    mstab::block_totals(nactive, noverflow, first.at, P.active, P.overflow, P.first);
 }
 
-static __global__ void bitwise_col_finish(ColParams P) {
-    const uint64_t overflow = *P.overflow, first = *P.first;
-    msrg::LimbReport r;
-    r.overflow = overflow;
-    r.first_overflow_row = overflow ? (first & 0xFFFFFFFFull) : 0;
-    r.first_overflow_spec = overflow ? (uint32_t)(first >> 32) : 0;
-    r.pad = 0;
-    r.active = *P.active;
-    *P.report = r;
-}
+static __global__ void bitwise_col_finish(ColParams P) { msdc::write_limb_report(P); }
 
 // ---- the table ----------------------------------------------------------------------------------------------------------------------
 struct TableParams {
@@ -145,10 +122,10 @@ __global__ void __launch_bounds__(NT) bitwise_table(TableParams P) {
         const unsigned s = r >> (2 * P.bits);
         const unsigned op = s == 0 ? P.ops[0] : s == 1 ? P.ops[1] : P.ops[2];
         const uint32_t x = (r >> P.bits) & lmask, y = r & lmask;
-        if (P.top) F::store(P.top, j, msrg::limb_elem<F>(op));
-        F::store(P.tx, j, msrg::limb_elem<F>(x));
-        F::store(P.ty, j, msrg::limb_elem<F>(y));
-        F::store(P.tz, j, msrg::limb_elem<F>((uint32_t)apply(op, x, y)));
+        if (P.top) F::store(P.top, j, msdc::limb_elem<F>(op));
+        F::store(P.tx, j, msdc::limb_elem<F>(x));
+        F::store(P.ty, j, msdc::limb_elem<F>(y));
+        F::store(P.tz, j, msdc::limb_elem<F>((uint32_t)apply(op, x, y)));
     }
 }
 
@@ -178,7 +155,7 @@ __device__ __forceinline__ bool load_operands(const Set& L, size_t i, unsigned b
     mstab::Canon<V>::words(L.a, i, wa);
     mstab::Canon<V>::words(L.b, i, wb);
     const unsigned total = L.nlimbs * bits;
-    bool ok = !msrg::above<V>(wa, total) && !msrg::above<V>(wb, total);
+    bool ok = !msdc::above<V>(wa, total) && !msdc::above<V>(wb, total);
     if (L.c) {
         uint64_t wc[V], diff = 0;
         mstab::Canon<V>::words(L.c, i, wc);
@@ -190,7 +167,7 @@ __device__ __forceinline__ bool load_operands(const Set& L, size_t i, unsigned b
 }
 
 // the low `bits` bits of the 64 V-bit integer w, which is shifted right by as many: 1 <= bits <= 12.  The limbs of a row come out one
-// after another, a limb that straddles two words included, and every index is a constant: msrg::limb_at picks the word a limb starts in,
+// after another, a limb that straddles two words included, and every index is a constant: range_kernels.h's limb_at picks the word a limb starts in,
 // which here, with two operands in flight, made the compiler keep both in LDS (and in scratch where the histogram left no room).
 template <int V>
 __device__ __forceinline__ uint32_t pop_limb(uint64_t* w, unsigned bits) {
@@ -207,7 +184,8 @@ __global__ void __launch_bounds__(NT) bitwise_count_plain(CountParams P) {
     const Set& L = P.sets[blockIdx.y];
     const unsigned bits = P.bits, nlimbs = L.nlimbs;
     uint32_t* cnt = P.cnt + ((size_t)L.slot << (2 * bits));
-    uint64_t missing = 0, first = ~0ull;
+    uint64_t missing = 0;
+    mstab::FirstRow first{~0ull};
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < P.n; i += (size_t)gridDim.x * NT) {
         uint64_t wa[V], wb[V];
         #pragma unroll
@@ -215,31 +193,26 @@ __global__ void __launch_bounds__(NT) bitwise_count_plain(CountParams P) {
         bool counted = false;
         if (mask_holds<V>(L.mask, L.mask_kind, i)) {
             counted = load_operands<V>(L, i, bits, wa, wb);
-            if (!counted) {
-                missing++;
-                const uint64_t at = (uint64_t)blockIdx.y << 32 | (uint64_t)i;
-                if (at < first) first = at;
-            }
+            if (!counted) { missing++; first.see(blockIdx.y, i); }
         }
         for (unsigned j = 0; j < nlimbs; j++) {                                // the same trip count on every lane that is here
             const uint32_t x = pop_limb<V>(wa, bits), y = pop_limb<V>(wb, bits);
             mslk::count_found<true>(cnt, counted ? (x << bits | y) : mslk::EMPTY);
         }
     }
-    if (missing) { add(P.missing, missing); amin(P.first, first); }
+    if (missing) { add(P.missing, missing); amin(P.first, first.at); }
 }
 
 // grid (G, nops): workgroup (g, slot) takes rows g * LNT + lane, + G * LNT, ... of every set of that slot.  2 bits <= HB.
 template <int V, int HB>
 __global__ void __launch_bounds__(LNT) bitwise_count_lds(CountParams P) {
-    constexpr unsigned WORDS = HB <= 15 ? 1u << HB : 1u << 15;
-    __shared__ uint32_t hist[WORDS];
+    __shared__ uint32_t hist[msdc::hist_words<HB>];
     const unsigned bits = P.bits, slot = blockIdx.y;
     const unsigned nwords = HB <= 15 ? 1u << (2 * bits) : 1u << 15;
     uint32_t* cnt = P.cnt + ((size_t)slot << (2 * bits));
-    for (unsigned k = threadIdx.x; k < nwords; k += LNT) hist[k] = 0;
-    __syncthreads();
-    uint64_t missing = 0, first = ~0ull;
+    msdc::hist_clear(hist, nwords);
+    uint64_t missing = 0;
+    mstab::FirstRow first{~0ull};
     unsigned pending = 0;                                                      // increments a lane may have made since the last flush
     for (unsigned s = 0; s < P.nsets; s++) {
         const Set& L = P.sets[s];
@@ -250,15 +223,11 @@ __global__ void __launch_bounds__(LNT) bitwise_count_lds(CountParams P) {
             const size_t i = row0 + threadIdx.x;
             if (i < P.n && mask_holds<V>(L.mask, L.mask_kind, i)) {
                 uint64_t wa[V], wb[V];
-                if (!load_operands<V>(L, i, bits, wa, wb)) {
-                    missing++;
-                    const uint64_t at = (uint64_t)s << 32 | (uint64_t)i;
-                    if (at < first) first = at;
-                } else {
+                if (!load_operands<V>(L, i, bits, wa, wb)) { missing++; first.see(s, i); }
+                else {
                     for (unsigned j = 0; j < nlimbs; j++) {
-                        const uint32_t x = pop_limb<V>(wa, bits), y = pop_limb<V>(wb, bits), bin = x << bits | y;
-                        if (HB <= 15) add(hist + bin, 1u);
-                        else add(hist + (bin >> 1), 1u << (16 * (bin & 1u)));
+                        const uint32_t x = pop_limb<V>(wa, bits), y = pop_limb<V>(wb, bits);
+                        msdc::hist_add<HB>(hist, x << bits | y);
                     }
                 }
             }
@@ -268,28 +237,19 @@ __global__ void __launch_bounds__(LNT) bitwise_count_lds(CountParams P) {
             // row's set is, it adds at most max_limbs.
             if (HB > 15) {
                 pending += nlimbs;
-                if (pending + P.max_limbs > (unsigned)FLUSH_INCS) { msrg::flush_bins<HB>(hist, cnt, nwords); pending = 0; }
+                if (pending + P.max_limbs > (unsigned)FLUSH_INCS) { msdc::flush_bins<HB>(hist, cnt, nwords); pending = 0; }
             }
         }
     }
-    msrg::flush_bins<HB>(hist, cnt, nwords);
-    if (missing) { add(P.missing, missing); amin(P.first, first); }
+    msdc::flush_bins<HB>(hist, cnt, nwords);
+    if (missing) { add(P.missing, missing); amin(P.first, first.at); }
 }
 
 template <class F>
 __global__ void __launch_bounds__(NT) bitwise_finish(CountParams P) {
     for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < P.n_m; j += (size_t)gridDim.x * NT)
         F::store(P.m, j, mslk::from_count<F>(j < P.T ? P.cnt[j] : 0u));
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const uint64_t missing = *P.missing, first = *P.first;
-        mslk::Report r;
-        r.missing = missing;
-        r.first_missing_row = missing ? (first & 0xFFFFFFFFull) : 0;
-        r.first_missing_set = missing ? (uint32_t)(first >> 32) : 0;
-        r.pad = 0;
-        r.duplicate_table_rows = 0;
-        *P.report = r;
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) mslk::write_report(P.report, *P.missing, *P.first, 0);
 }
 
 }  // namespace msbw

@@ -25,6 +25,7 @@ using mslk::Key;
 using mstab::mask_holds;
 using mstab::add;
 using mstab::amin;
+using mstab::block_totals;
 
 static constexpr uint32_t NONE = 0xFFFFFFFFu;
 
@@ -44,36 +45,6 @@ struct Params {
     unsigned width;
 };
 
-// sums and a minimum of one value per lane -> one add / amin per workgroup, through the wave and LDS; every thread of the workgroup calls it
-__device__ __forceinline__ void block_totals(uint64_t a, uint64_t b, uint64_t lo, uint64_t* sum_a, uint64_t* sum_b, uint64_t* min_lo) {
-    __shared__ uint64_t s_q[3];
-    if (threadIdx.x == 0) { s_q[0] = 0; s_q[1] = 0; s_q[2] = ~0ull; }
-    __syncthreads();
-#ifndef MS_EMU
-    #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        a += (uint64_t)__shfl_xor((unsigned long long)a, d);
-        b += (uint64_t)__shfl_xor((unsigned long long)b, d);
-        const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)lo, d);
-        lo = lo < o ? lo : o;
-    }
-    const bool speaker = (threadIdx.x & 63u) == 0;
-#else
-    const bool speaker = true;
-#endif
-    if (speaker) {
-        if (a) add(&s_q[0], a);
-        if (b) add(&s_q[1], b);
-        if (lo != ~0ull) amin(&s_q[2], lo);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (s_q[0]) add(sum_a, s_q[0]);
-        if (sum_b && s_q[1]) add(sum_b, s_q[1]);
-        if (min_lo && s_q[2] != ~0ull) amin(min_lo, s_q[2]);
-    }
-}
-
 template <int V>
 __global__ void __launch_bounds__(NT) join_table_active(Params P) {
     uint64_t act = 0;
@@ -87,7 +58,8 @@ __global__ void __launch_bounds__(NT) join_match(Params P) {
     const Tuple& L = P.sets[blockIdx.y];
     uint32_t* const out = P.match[blockIdx.y];
     const unsigned width = P.width;
-    uint64_t matched = 0, missing = 0, first = ~0ull;
+    uint64_t matched = 0, missing = 0;
+    mstab::FirstRow first{~0ull};
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < P.n; i += (size_t)gridDim.x * NT) {
         uint32_t found = NONE;
         if (mask_holds<V>(L.mask, L.mask_kind, i)) {
@@ -97,8 +69,7 @@ __global__ void __launch_bounds__(NT) join_match(Params P) {
                 const uint32_t cur = P.slots[s];                       // the table is finished: a plain load
                 if (cur == EMPTY) {
                     missing++;
-                    const uint64_t at = (uint64_t)blockIdx.y << 32 | (uint64_t)i;
-                    if (at < first) first = at;
+                    first.see(blockIdx.y, i);
                     break;
                 }
                 if (mslk::same_key<V>(P.table, width, cur, k)) { found = cur; matched++; break; }
@@ -107,17 +78,17 @@ __global__ void __launch_bounds__(NT) join_match(Params P) {
         }
         out[i] = found;
     }
-    block_totals(matched, missing, first, P.matched, P.missing, P.first);
+    block_totals(matched, missing, first.at, P.matched, P.missing, P.first);
 }
 
 __global__ void join_finish(Params P) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const uint64_t missing = *P.missing, first = *P.first;
+    const mstab::FirstRow first{*P.first};
     Report r;
     r.matched = *P.matched;
-    r.missing = missing;
-    r.first_missing_row = missing ? (first & 0xFFFFFFFFull) : 0;
-    r.first_missing_set = missing ? (uint32_t)(first >> 32) : 0;
+    r.missing = *P.missing;
+    r.first_missing_row = first.row();
+    r.first_missing_set = first.group();
     r.pad = 0;
     r.duplicate_table_rows = *P.dups;
     r.table_active = P.table.mask_kind == mstab::MASK_ALWAYS ? (uint64_t)P.n_table : *P.tact;

@@ -142,7 +142,8 @@ template <int V, bool AGG>
 __global__ void __launch_bounds__(NT) lookup_count(Params P) {
     const Tuple& L = P.sets[blockIdx.y];
     const unsigned width = P.width;
-    uint64_t missing = 0, first = ~0ull;
+    uint64_t missing = 0;
+    mstab::FirstRow first{~0ull};
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < P.n; i += (size_t)gridDim.x * NT) {
         uint32_t found = EMPTY;
         if (mask_holds<V>(L.mask, L.mask_kind, i)) {
@@ -152,8 +153,7 @@ __global__ void __launch_bounds__(NT) lookup_count(Params P) {
                 const uint32_t cur = P.slots[s];
                 if (cur == EMPTY) {
                     missing++;
-                    const uint64_t at = (uint64_t)blockIdx.y << 32 | (uint64_t)i;
-                    if (at < first) first = at;
+                    first.see(blockIdx.y, i);
                     break;
                 }
                 if (same_key<V>(P.table, width, cur, k)) { found = cur; break; }
@@ -162,26 +162,29 @@ __global__ void __launch_bounds__(NT) lookup_count(Params P) {
         }
         count_found<AGG>(P.cnt, found);
     }
-    if (missing) { add(P.missing, missing); amin(P.first, first); }
+    if (missing) { add(P.missing, missing); amin(P.first, first.at); }
 }
 
 template <class F> __device__ __forceinline__ typename F::T from_count(uint32_t c);
 template <> __device__ __forceinline__ uint64_t from_count<msstage::FpT>(uint32_t c) { return gl::to_mont((uint64_t)c); }
 template <> __device__ __forceinline__ f252::E from_count<msstage::Fp252T>(uint32_t c) { return c ? f252::to_mont(f252::E{{(uint64_t)c, 0, 0, 0}}) : f252::zero(); }
 
+// one lane of a finish kernel: the report of a count, from its `missing` and the amin over the missing rows of (set << 32 | row)
+__device__ __forceinline__ void write_report(Report* report, uint64_t missing, uint64_t first_at, uint64_t dups) {
+    const mstab::FirstRow first{first_at};
+    Report r;
+    r.missing = missing;
+    r.first_missing_row = first.row();
+    r.first_missing_set = first.group();
+    r.pad = 0;
+    r.duplicate_table_rows = dups;
+    *report = r;
+}
+
 template <class F>
 __global__ void __launch_bounds__(NT) lookup_finish(Params P) {
     for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < P.n; j += (size_t)gridDim.x * NT) F::store(P.m, j, from_count<F>(P.cnt[j]));
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const uint64_t missing = *P.missing, first = *P.first;
-        Report r;
-        r.missing = missing;
-        r.first_missing_row = missing ? (first & 0xFFFFFFFFull) : 0;
-        r.first_missing_set = missing ? (uint32_t)(first >> 32) : 0;
-        r.pad = 0;
-        r.duplicate_table_rows = *P.dups;
-        *P.report = r;
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) write_report(P.report, *P.missing, *P.first, *P.dups);
 }
 
 }  // namespace mslk

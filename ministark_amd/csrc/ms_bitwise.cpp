@@ -3,10 +3,11 @@
 #include "ms_internal.h"
 #include "../../include/ministark_hip_bitwise.h"
 #include "bitwise_kernels.h"
+#include "count_args.h"
 
 static_assert(msbw::MAXSPECS == (int)MS_BITWISE_MAX_SPECS && msbw::MAXSETS == (int)MS_BITWISE_MAX_SETS && msbw::MAXOPS == (int)MS_BITWISE_MAX_OPS, "bitwise_kernels.h and the header disagree");
 static_assert(msbw::OP_AND == (int)MS_BIT_AND && msbw::OP_OR == (int)MS_BIT_OR && msbw::OP_XOR == (int)MS_BIT_XOR, "op codes");
-static_assert(sizeof(ms_bitwise_spec) == 32 && sizeof(ms_bitwise_set) == 32 && sizeof(msbw::Spec) == 40 && sizeof(msrg::LimbReport) == sizeof(ms_limb_report), "record layouts");
+static_assert(sizeof(ms_bitwise_spec) == 32 && sizeof(ms_bitwise_set) == 32 && sizeof(msbw::Spec) == 40 && sizeof(msdc::LimbReport) == sizeof(ms_limb_report), "record layouts");
 static_assert(sizeof(msbw::CountParams) <= 3584, "the sets travel as a kernel argument");
 static_assert(MS_BITWISE_MAX_BITS == 12 && MS_BITWISE_MAX_TABLE_LOG == 24, "a bin is a uint32 below mslk::EMPTY; a limb pair is 24 bits");
 static_assert(2 * msbw::PACKED_BITS == 16, "the packed histogram has 2^16 bins");
@@ -46,6 +47,8 @@ extern "C" int ms_bitwise_columns(ms_ctx* ctx, int field, size_t n, void* const*
     MSCHK(R.null_check());
     const ms_bitwise_spec* H = (const ms_bitwise_spec*)h_specs;
     std::vector<msbw::Spec> specs(nspecs);
+    std::vector<mscount::Dst> dst(nspecs);
+    double bytes = 0;                                                 // the operands (once when a == b), the mask, the result
     for (unsigned k = 0; k < nspecs; k++) {
         char who[32];
         snprintf(who, sizeof who, "spec %u: ", k);
@@ -57,54 +60,13 @@ extern "C" int ms_bitwise_columns(ms_ctx* ctx, int field, size_t n, void* const*
         if (H[k].width < 1 || (unsigned)H[k].width > wmax_of(V)) return fail(MS_ERR_INVALID, "%s: %san operand has 1 .. %u bits, not %d", me, who, wmax_of(V), H[k].width);
         if (H[k].dst < 0 || (unsigned)H[k].dst >= nbase) return fail(MS_ERR_INVALID, "%s: %sdestination column %d out of range (%u)", me, who, H[k].dst, nbase);
         specs[k].dst = (uint32_t)H[k].dst; specs[k].width = (uint32_t)H[k].width; specs[k].op = (uint32_t)H[k].op; specs[k].mask_kind = H[k].mask;
+        dst[k] = {specs[k].dst, specs[k].dst + 1};
+        bytes += ((specs[k].a == specs[k].b ? 1.0 : 2.0) + (specs[k].mask ? 1.0 : 0.0) + 1.0) * (double)(n * V * 8);
     }
-    const size_t col_bytes = n * V * 8;
-    for (unsigned k = 0; k < nspecs; k++) {
-        const unsigned d = specs[k].dst;
-        for (unsigned t = 0; t < k; t++)
-            if (specs[t].dst == d || ranges_overlap(d_base[d], col_bytes, d_base[specs[t].dst], col_bytes))
-                return fail(MS_ERR_INVALID, "%s: the destination columns of specs %u and %u overlap", me, t, k);
-        for (unsigned c : R.used)
-            if (c == d || ranges_overlap(d_base[d], col_bytes, d_base[c], col_bytes))
-                return fail(MS_ERR_INVALID, "%s: spec %u: destination column %u and column %u, which a spec reads as an operand or its mask, overlap", me, k, d, c);
-        if (ranges_overlap(d_report, sizeof(ms_limb_report), d_base[d], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_report and base column %u overlap", me, d);
-    }
-    for (unsigned c : R.used)
-        if (ranges_overlap(d_report, sizeof(ms_limb_report), d_base[c], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_report and base column %u overlap", me, c);
-    if (n && nspecs) MSCHK(canon_named(ctx, me, field, n, (const void* const*)d_base, R.used));      // what the call reads: the destinations may hold anything
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    if (n == 0 || nspecs == 0) {
-        HIPCHK(hipMemsetAsync(d_report, 0, sizeof(ms_limb_report), ctx->stream));
-        return MS_OK;
-    }
-    LockedPoolGuard pooled(ctx);
-    // [specs | the pointer table] as the kernel reads them; [overflow | active] zero, [first] all ones
-    const size_t spec_bytes = nspecs * sizeof(msbw::Spec);
-    std::vector<char> tab(spec_bytes + (size_t)nbase * sizeof(void*));
-    memcpy(tab.data(), specs.data(), spec_bytes);
-    memcpy(tab.data() + spec_bytes, d_base, (size_t)nbase * sizeof(void*));
-    const void* d_tab = nullptr;
-    MSCHK(stage_view(ctx, tab.data(), tab.size(), &d_tab, pooled));
-    void* tmp = nullptr;
-    MSCHK(pooled.alloc(24, &tmp));
-    msbw::ColParams P;
-    memset(&P, 0, sizeof P);
-    P.specs = (const msbw::Spec*)d_tab; P.base = (uint64_t* const*)((const char*)d_tab + spec_bytes);
-    P.overflow = (uint64_t*)tmp; P.active = (uint64_t*)tmp + 1; P.first = (uint64_t*)tmp + 2;
-    P.report = (msrg::LimbReport*)d_report; P.n = n;
-    { ProfScope ps(ctx, "bitwise_clear", 24.0);
-      HIPCHK(hipMemsetAsync(tmp, 0, 16, ctx->stream));
-      HIPCHK(hipMemsetAsync((char*)tmp + 16, 0xFF, 8, ctx->stream)); }
-    double bytes = 0;                                                 // the operands (once when a == b), the mask, the result
-    for (unsigned k = 0; k < nspecs; k++) bytes += ((specs[k].a == specs[k].b ? 1.0 : 2.0) + (specs[k].mask ? 1.0 : 0.0) + 1.0) * (double)col_bytes;
-    { ProfScope ps(ctx, "bitwise_columns", bytes);
-      if (V == 1) hipLaunchKernelGGL((msbw::bitwise_columns<msstage::FpT>), dim3(stream_grid(n), nspecs), dim3(msbw::NT), 0, ctx->stream, P);
-      else hipLaunchKernelGGL((msbw::bitwise_columns<msstage::Fp252T>), dim3(stream_grid(n), nspecs), dim3(msbw::NT), 0, ctx->stream, P); }
-    { ProfScope ps(ctx, "bitwise_col_finish", 24.0 + sizeof(ms_limb_report));
-      hipLaunchKernelGGL(msbw::bitwise_col_finish, dim3(1), dim3(1), 0, ctx->stream, P); }
-    HIPCHK(hipGetLastError());
-    return MS_OK;
+    // two destination columns clash by address too, and d_report meets a spec's destination before the next spec is looked at
+    static const mscount::Writer<msbw::Spec> W = {"an operand or its mask", "bitwise_clear", "bitwise_columns", "bitwise_col_finish",
+        msbw::bitwise_columns<msstage::FpT>, msbw::bitwise_columns<msstage::Fp252T>, msbw::bitwise_col_finish, true, true};
+    return mscount::write_columns(ctx, R, W, field, V, n, d_base, specs, dst, d_report, bytes);
 }
 
 extern "C" int ms_bitwise_table(ms_ctx* ctx, int field, unsigned bits, const void* h_op_codes, unsigned nops, size_t n_t,
@@ -138,20 +100,12 @@ extern "C" int ms_bitwise_table(ms_ctx* ctx, int field, unsigned bits, const voi
     return MS_OK;
 }
 
-// The workgroups per op slot of the LDS form.  Each ends with one global add per non-zero bin of its histogram, up to 4^bits of them: G
-// workgroups on each of nops slots flush up to G * nops * 4^bits adds, whatever the rows were, where the count itself is one LDS add per
-// increment.  G is the largest number that keeps the flushes at a quarter of the increments counted, at most `cap` workgroups in all --
-// what the device holds at once -- and at most one per LNT rows.
-static unsigned lds_grid(size_t n, unsigned long long incs, unsigned bits, unsigned nops, unsigned cap) {
-    unsigned long long g = incs / (((unsigned long long)nops * 4ull) << (2 * bits));
-    g = std::min<unsigned long long>(g, (n + msbw::LNT - 1) / msbw::LNT);
-    return (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>(g, cap / nops));
-}
-
 template <int V, class F>
 static void bitwise_launch(ms_ctx* ctx, const msbw::CountParams& P, unsigned nops, unsigned long long incs, bool lds) {
     using namespace msbw;
     const double rows = (double)P.n * P.nsets;
+    // per op slot: each of G workgroups on each of nops slots flushes up to 4^bits bins, and `cap` workgroups in all
+    auto lds_grid = [&](unsigned cap) { return mscount::lds_grid(P.n, incs, ((unsigned long long)nops * 4ull) << (2 * P.bits), cap / nops); };
     if (P.n && P.nsets) {
         if (!lds) {
             ProfScope ps(ctx, "bitwise_count_plain", rows * 24.0 * V + 4.0 * (double)incs);
@@ -159,9 +113,9 @@ static void bitwise_launch(ms_ctx* ctx, const msbw::CountParams& P, unsigned nop
         } else {
             ProfScope ps(ctx, "bitwise_count_lds", rows * 24.0 * V);
             // 16 KiB histograms: two workgroups of 1024 lanes fill a CU's 32 wave slots; 64 and 128 KiB ones: one per CU
-            if (P.bits <= 6) hipLaunchKernelGGL((bitwise_count_lds<V, 12>), dim3(lds_grid(P.n, incs, P.bits, nops, 512), nops), dim3(LNT), 0, ctx->stream, P);
-            else if (P.bits == 7) hipLaunchKernelGGL((bitwise_count_lds<V, 14>), dim3(lds_grid(P.n, incs, P.bits, nops, 256), nops), dim3(LNT), 0, ctx->stream, P);
-            else hipLaunchKernelGGL((bitwise_count_lds<V, 16>), dim3(lds_grid(P.n, incs, P.bits, nops, 256), nops), dim3(LNT), 0, ctx->stream, P);
+            if (P.bits <= 6) hipLaunchKernelGGL((bitwise_count_lds<V, 12>), dim3(lds_grid(512), nops), dim3(LNT), 0, ctx->stream, P);
+            else if (P.bits == 7) hipLaunchKernelGGL((bitwise_count_lds<V, 14>), dim3(lds_grid(256), nops), dim3(LNT), 0, ctx->stream, P);
+            else hipLaunchKernelGGL((bitwise_count_lds<V, 16>), dim3(lds_grid(256), nops), dim3(LNT), 0, ctx->stream, P);
         }
     }
     { ProfScope ps(ctx, "bitwise_finish", 4.0 * (double)P.T + 8.0 * V * (double)P.n_m);
@@ -209,36 +163,10 @@ extern "C" int ms_bitwise_multiplicities(ms_ctx* ctx, int field, size_t n, const
     if (n > ((size_t)1 << 32)) return fail(MS_ERR_UNSUPPORTED, "%s: %zu rows (at most 2^32: the first missing row travels as set << 32 | row)", me, n);
     const unsigned long long incs = limbs * (unsigned long long)n;   // limbs <= 2^14, n <= 2^32: no wrap
     if (incs >= (1ull << 32)) return fail(MS_ERR_UNSUPPORTED, "%s: %llu limbs a row over %zu rows (the counters are 32-bit: the limb pairs of a call are fewer than 2^32)", me, limbs, n);
-    const size_t col_bytes = n * V * 8, m_bytes = n_m * V * 8;
-    for (unsigned c : R.used) {
-        if (ranges_overlap(d_m, m_bytes, d_base[c], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_m and base column %u, which a set or a mask names, overlap", me, c);
-        if (ranges_overlap(d_report, sizeof(ms_lookup_report), d_base[c], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_report and base column %u overlap", me, c);
-    }
-    if (ranges_overlap(d_m, m_bytes, d_report, sizeof(ms_lookup_report))) return fail(MS_ERR_INVALID, "%s: d_m and d_report overlap", me);
-    MSCHK(canon_named(ctx, me, field, n, d_base, R.used));            // only what the call reads: d_m may be a column of d_base, of any content
-    // MS_BITWISE_FORM=plain|lds: the counting kernel scripts/bitwise_probe.py asks for; otherwise the LDS histogram wherever it exists
-    const bool has_lds = bits <= (unsigned)msbw::PACKED_BITS;
-    bool lds = has_lds;
-    if (const char* form = getenv("MS_BITWISE_FORM")) {
-        if (!strcmp(form, "plain")) lds = false;
-        else if (strcmp(form, "lds")) return fail(MS_ERR_INVALID, "%s: MS_BITWISE_FORM is plain or lds, not %s", me, form);
-    }
-    lds = lds && has_lds;                                             // above 2^16 bins an op there is the global form alone
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    LockedPoolGuard pooled(ctx);
-    // [first] all ones, [missing | cnt[T]] zero
-    void* tmp = nullptr;
-    const size_t zero_bytes = 8 + 4 * T;
-    MSCHK(pooled.alloc(8 + zero_bytes, &tmp));
-    P.first = (uint64_t*)tmp; P.missing = (uint64_t*)tmp + 1; P.cnt = (uint32_t*)((uint64_t*)tmp + 2);
-    P.m = (uint64_t*)d_m; P.report = (mslk::Report*)d_report;
-    P.n = n; P.n_m = n_m; P.T = T; P.bits = bits; P.nsets = nsets;
-    { ProfScope ps(ctx, "bitwise_clear", (double)(8 + zero_bytes));
-      HIPCHK(hipMemsetAsync(tmp, 0xFF, 8, ctx->stream));
-      HIPCHK(hipMemsetAsync((char*)tmp + 8, 0, zero_bytes, ctx->stream)); }
-    if (V == 1) bitwise_launch<1, msstage::FpT>(ctx, P, nops, incs, lds);
-    else bitwise_launch<4, msstage::Fp252T>(ctx, P, nops, incs, lds);
-    HIPCHK(hipGetLastError());
-    return MS_OK;
+    P.T = T; P.bits = bits; P.nsets = nsets;
+    // above 2^16 bins an op there is the global form alone
+    return mscount::count_scratch(ctx, R, field, V, n, n_m, d_m, d_report, "MS_BITWISE_FORM", bits <= (unsigned)msbw::PACKED_BITS, T, "bitwise_clear", P, [&](bool lds) {
+        if (V == 1) bitwise_launch<1, msstage::FpT>(ctx, P, nops, incs, lds);
+        else bitwise_launch<4, msstage::Fp252T>(ctx, P, nops, incs, lds);
+    });
 }

@@ -3,9 +3,10 @@
 #include "ms_internal.h"
 #include "../../include/ministark_hip_range.h"
 #include "range_kernels.h"
+#include "count_args.h"
 
 static_assert(msrg::MAXSPECS == (int)MS_RANGE_MAX_SPECS && msrg::MAXSETS == (int)MS_RANGE_MAX_SETS, "range_kernels.h and the header disagree");
-static_assert(sizeof(ms_limb_spec) == 32 && sizeof(ms_range_set) == 16 && sizeof(ms_limb_report) == 32 && sizeof(msrg::LimbReport) == sizeof(ms_limb_report), "record layouts");
+static_assert(sizeof(ms_limb_spec) == 32 && sizeof(ms_range_set) == 16 && sizeof(ms_limb_report) == 32 && sizeof(msdc::LimbReport) == sizeof(ms_limb_report), "record layouts");
 static_assert(sizeof(mslk::Report) == sizeof(ms_lookup_report) && sizeof(msrg::Spec) == 32, "record layouts");
 static_assert(MS_RANGE_MAX_LIMB_BITS == 32 && MS_RANGE_MAX_TABLE_BITS == 24, "a limb is a uint32; no bin is mslk::EMPTY");
 
@@ -22,6 +23,8 @@ extern "C" int ms_limb_decompose(ms_ctx* ctx, int field, size_t n, void* const* 
     MSCHK(R.null_check());
     const ms_limb_spec* H = (const ms_limb_spec*)h_specs;
     std::vector<msrg::Spec> specs(nspecs);
+    std::vector<mscount::Dst> dst(nspecs);
+    double bytes = 0;                                                 // the source, the mask, every limb column
     for (unsigned k = 0; k < nspecs; k++) {
         char who[32];
         snprintf(who, sizeof who, "spec %u: ", k);
@@ -35,73 +38,21 @@ extern "C" int ms_limb_decompose(ms_ctx* ctx, int field, size_t n, void* const* 
         if (H[k].dst0 < 0 || (unsigned)H[k].dst0 >= nbase || (unsigned)H[k].nlimbs > nbase - (unsigned)H[k].dst0)
             return fail(MS_ERR_INVALID, "%s: %sdestination columns %d .. %lld out of range (%u)", me, who, H[k].dst0, (long long)H[k].dst0 + H[k].nlimbs - 1, nbase);
         specs[k].dst0 = (uint32_t)H[k].dst0; specs[k].nlimbs = (uint32_t)H[k].nlimbs; specs[k].bits = (uint32_t)H[k].bits; specs[k].mask_kind = H[k].mask;
+        dst[k] = {specs[k].dst0, specs[k].dst0 + specs[k].nlimbs};
+        bytes += (1.0 + (specs[k].mask ? 1.0 : 0.0) + specs[k].nlimbs) * (double)(n * V * 8);
     }
-    const size_t col_bytes = n * V * 8;
-    for (unsigned k = 0; k < nspecs; k++) {
-        const unsigned d0 = specs[k].dst0, d1 = d0 + specs[k].nlimbs;
-        for (unsigned t = 0; t < k; t++)
-            if (d0 < specs[t].dst0 + specs[t].nlimbs && specs[t].dst0 < d1)
-                return fail(MS_ERR_INVALID, "%s: the destination columns of specs %u and %u overlap", me, t, k);
-        for (unsigned d = d0; d < d1; d++)
-            for (unsigned c : R.used)
-                if (c == d || ranges_overlap(d_base[d], col_bytes, d_base[c], col_bytes))
-                    return fail(MS_ERR_INVALID, "%s: spec %u: destination column %u and column %u, which a spec reads as its source or its mask, overlap", me, k, d, c);
-    }
-    for (unsigned c : R.used)
-        if (ranges_overlap(d_report, sizeof(ms_limb_report), d_base[c], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_report and base column %u overlap", me, c);
-    for (unsigned k = 0; k < nspecs; k++)
-        for (unsigned d = specs[k].dst0; d < specs[k].dst0 + specs[k].nlimbs; d++)
-            if (ranges_overlap(d_report, sizeof(ms_limb_report), d_base[d], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_report and base column %u overlap", me, d);
-    if (n && nspecs) MSCHK(canon_named(ctx, me, field, n, (const void* const*)d_base, R.used));      // what the call reads: the destinations may hold anything
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    if (n == 0 || nspecs == 0) {
-        HIPCHK(hipMemsetAsync(d_report, 0, sizeof(ms_limb_report), ctx->stream));
-        return MS_OK;
-    }
-    LockedPoolGuard pooled(ctx);
-    // [specs | the pointer table] as the kernel reads them; [overflow | active] zero, [first] all ones
-    const size_t spec_bytes = nspecs * sizeof(msrg::Spec);
-    std::vector<char> tab(spec_bytes + (size_t)nbase * sizeof(void*));
-    memcpy(tab.data(), specs.data(), spec_bytes);
-    memcpy(tab.data() + spec_bytes, d_base, (size_t)nbase * sizeof(void*));
-    const void* d_tab = nullptr;
-    MSCHK(stage_view(ctx, tab.data(), tab.size(), &d_tab, pooled));
-    void* tmp = nullptr;
-    MSCHK(pooled.alloc(24, &tmp));
-    msrg::LimbParams P;
-    memset(&P, 0, sizeof P);
-    P.specs = (const msrg::Spec*)d_tab; P.base = (uint64_t* const*)((const char*)d_tab + spec_bytes);
-    P.overflow = (uint64_t*)tmp; P.active = (uint64_t*)tmp + 1; P.first = (uint64_t*)tmp + 2;
-    P.report = (msrg::LimbReport*)d_report; P.n = n;
-    { ProfScope ps(ctx, "limb_clear", 24.0);
-      HIPCHK(hipMemsetAsync(tmp, 0, 16, ctx->stream));
-      HIPCHK(hipMemsetAsync((char*)tmp + 16, 0xFF, 8, ctx->stream)); }
-    double bytes = 0;                                                 // the source, the mask, every limb column
-    for (unsigned k = 0; k < nspecs; k++) bytes += (1.0 + (specs[k].mask ? 1.0 : 0.0) + specs[k].nlimbs) * (double)col_bytes;
-    { ProfScope ps(ctx, "limb_decompose", bytes);
-      if (V == 1) hipLaunchKernelGGL((msrg::limb_decompose<msstage::FpT>), dim3(stream_grid(n), nspecs), dim3(msrg::NT), 0, ctx->stream, P);
-      else hipLaunchKernelGGL((msrg::limb_decompose<msstage::Fp252T>), dim3(stream_grid(n), nspecs), dim3(msrg::NT), 0, ctx->stream, P); }
-    { ProfScope ps(ctx, "limb_finish", 24.0 + sizeof(ms_limb_report));
-      hipLaunchKernelGGL(msrg::limb_finish, dim3(1), dim3(1), 0, ctx->stream, P); }
-    HIPCHK(hipGetLastError());
-    return MS_OK;
-}
-
-// The workgroups of the LDS form.  Each ends with one global add per non-zero bin of its histogram, up to 2^bits of them: G workgroups
-// flush up to G * 2^bits adds, whatever the rows were, where the count itself is one LDS add per row.  G is the largest number that keeps
-// the flushes at a quarter of the rows counted, at most `cap` -- what the device holds at once -- and at most one per LNT rows.
-static unsigned lds_grid(size_t n, unsigned nsets, unsigned bits, unsigned cap) {
-    const unsigned long long rows = (unsigned long long)n * nsets;
-    unsigned long long g = rows / (4ull << bits);
-    g = std::min<unsigned long long>(g, (n + msrg::LNT - 1) / msrg::LNT);
-    return (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>(g, cap));
+    // two destination columns clash by index alone, and d_report meets the read columns before the destinations
+    static const mscount::Writer<msrg::Spec> W = {"its source or its mask", "limb_clear", "limb_decompose", "limb_finish",
+        msrg::limb_decompose<msstage::FpT>, msrg::limb_decompose<msstage::Fp252T>, msrg::limb_finish, false, false};
+    return mscount::write_columns(ctx, R, W, field, V, n, d_base, specs, dst, d_report, bytes);
 }
 
 template <int V, class F>
 static void range_launch(ms_ctx* ctx, const msrg::CountParams& P, bool lds) {
     using namespace msrg;
     const double rows = (double)P.n * P.nsets;
+    // each of G workgroups flushes up to 2^bits bins
+    auto lds_grid = [&](unsigned cap) { return mscount::lds_grid(P.n, (unsigned long long)P.n * P.nsets, 4ull << P.bits, cap); };
     if (P.n && P.nsets) {
         if (!lds) {
             ProfScope ps(ctx, "range_count_plain", rows * (8.0 * V + 4.0));
@@ -109,9 +60,9 @@ static void range_launch(ms_ctx* ctx, const msrg::CountParams& P, bool lds) {
         } else {
             ProfScope ps(ctx, "range_count_lds", rows * 8.0 * V);
             // 16 KiB histograms: two workgroups of 1024 lanes fill a CU's 32 wave slots; 128 KiB ones: one per CU
-            if (P.bits <= 12) hipLaunchKernelGGL((range_count_lds<V, 12>), dim3(lds_grid(P.n, P.nsets, P.bits, 512)), dim3(LNT), 0, ctx->stream, P);
-            else if (P.bits <= 15) hipLaunchKernelGGL((range_count_lds<V, 15>), dim3(lds_grid(P.n, P.nsets, P.bits, 256)), dim3(LNT), 0, ctx->stream, P);
-            else hipLaunchKernelGGL((range_count_lds<V, 16>), dim3(lds_grid(P.n, P.nsets, P.bits, 256)), dim3(LNT), 0, ctx->stream, P);
+            if (P.bits <= 12) hipLaunchKernelGGL((range_count_lds<V, 12>), dim3(lds_grid(512)), dim3(LNT), 0, ctx->stream, P);
+            else if (P.bits <= 15) hipLaunchKernelGGL((range_count_lds<V, 15>), dim3(lds_grid(256)), dim3(LNT), 0, ctx->stream, P);
+            else hipLaunchKernelGGL((range_count_lds<V, 16>), dim3(lds_grid(256)), dim3(LNT), 0, ctx->stream, P);
         }
     }
     { ProfScope ps(ctx, "range_finish", 4.0 * (double)((size_t)1 << P.bits) + 8.0 * V * (double)P.n_m);
@@ -142,34 +93,9 @@ extern "C" int ms_range_multiplicities(ms_ctx* ctx, int field, size_t n, const v
     }
     if (n > ((size_t)1 << 32)) return fail(MS_ERR_UNSUPPORTED, "%s: %zu rows (at most 2^32: the first missing row travels as set << 32 | row)", me, n);
     if ((unsigned long long)nsets * n >= (1ull << 32)) return fail(MS_ERR_UNSUPPORTED, "%s: %u sets of %zu rows (the counters are 32-bit: sets * rows < 2^32)", me, nsets, n);
-    const size_t col_bytes = n * V * 8, m_bytes = n_m * V * 8;
-    for (unsigned c : R.used) {
-        if (ranges_overlap(d_m, m_bytes, d_base[c], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_m and base column %u, which a set or a mask names, overlap", me, c);
-        if (ranges_overlap(d_report, sizeof(ms_lookup_report), d_base[c], col_bytes)) return fail(MS_ERR_INVALID, "%s: d_report and base column %u overlap", me, c);
-    }
-    if (ranges_overlap(d_m, m_bytes, d_report, sizeof(ms_lookup_report))) return fail(MS_ERR_INVALID, "%s: d_m and d_report overlap", me);
-    MSCHK(canon_named(ctx, me, field, n, d_base, R.used));            // only what the call reads: d_m may be a column of d_base, of any content
-    // MS_RANGE_FORM=plain|lds: the counting kernel scripts/range_probe.py asks for; otherwise the LDS histogram wherever it exists
-    bool lds = bits <= 16;
-    if (const char* form = getenv("MS_RANGE_FORM")) {
-        if (!strcmp(form, "plain")) lds = false;
-        else if (strcmp(form, "lds")) return fail(MS_ERR_INVALID, "%s: MS_RANGE_FORM is plain or lds, not %s", me, form);
-    }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    HIPCHK(hipSetDevice(ctx->device));
-    LockedPoolGuard pooled(ctx);
-    // [first] all ones, [missing | cnt[2^bits]] zero
-    void* tmp = nullptr;
-    const size_t zero_bytes = 8 + ((size_t)4 << bits);
-    MSCHK(pooled.alloc(8 + zero_bytes, &tmp));
-    P.first = (uint64_t*)tmp; P.missing = (uint64_t*)tmp + 1; P.cnt = (uint32_t*)((uint64_t*)tmp + 2);
-    P.m = (uint64_t*)d_m; P.report = (mslk::Report*)d_report;
-    P.n = n; P.n_m = n_m; P.bits = bits; P.nsets = nsets;
-    { ProfScope ps(ctx, "range_clear", (double)(8 + zero_bytes));
-      HIPCHK(hipMemsetAsync(tmp, 0xFF, 8, ctx->stream));
-      HIPCHK(hipMemsetAsync((char*)tmp + 8, 0, zero_bytes, ctx->stream)); }
-    if (V == 1) range_launch<1, msstage::FpT>(ctx, P, lds);
-    else range_launch<4, msstage::Fp252T>(ctx, P, lds);
-    HIPCHK(hipGetLastError());
-    return MS_OK;
+    P.bits = bits; P.nsets = nsets;
+    return mscount::count_scratch(ctx, R, field, V, n, n_m, d_m, d_report, "MS_RANGE_FORM", bits <= 16, (size_t)1 << bits, "range_clear", P, [&](bool lds) {
+        if (V == 1) range_launch<1, msstage::FpT>(ctx, P, lds);
+        else range_launch<4, msstage::Fp252T>(ctx, P, lds);
+    });
 }

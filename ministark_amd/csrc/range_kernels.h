@@ -2,25 +2,26 @@
 //   limb_decompose  grid (blocks, specs), grid-stride, one lane per row: the canonical words of the value once (Canon<V>::words), limb j =
 //                   bits [j * bits, (j + 1) * bits) of them -- a limb may straddle two 64-bit words -- back to Montgomery form, one coalesced
 //                   store per limb column.  The next row's words are loaded before this row's stores go out.  A lane counts its active
-//                   and its overflowing rows; a workgroup adds its sums once (block_totals: through the wave, then LDS).
+//                   and its overflowing rows; a workgroup adds its sums once (mstab::block_totals: through the wave, then LDS).
 //   limb_finish     one lane: the report.
 //   range_count_plain  grid (blocks, sets), grid-stride, one lane per row: cnt[v] += 1 in global memory through mslk::count_found, which
 //                   adds once for the lanes of a wave that hit the wave's first bin.  Correct for every `bits`.
 //   range_count_lds    G workgroups of LNT lanes, each over its share of the rows of EVERY set: a histogram of its own in LDS, then one
 //                   global add per non-zero bin.  HB <= 15: 2^HB 32-bit counters, which cannot overflow (sets * rows < 2^32).  HB = 16:
 //                   2^16 16-bit counters, two to a word, flushed after at most FLUSH_ROUNDS * LNT <= 65 535 counted rows, so that the
-//                   low half never carries into the high one.  No workgroup waits on another.
+//                   low half never carries into the high one.  No workgroup waits on another.  The histogram itself is direct_count.h's.
 //   range_finish    grid-stride: counter -> field element -> d_m, zero past the table; lane 0 writes the report.
 // A value is in the table when it is below 2^bits AS AN INTEGER: every word above the first has to be zero.
 // Integer adds and mins commute: counters and reports are the same on every run.  Every atomic is table_common.h's (plain
-// read-modify-write under MS_EMU, where the lanes of a launch run one after another).
+// read-modify-write under MS_EMU, where the lanes of a launch run one after another).  above, limb_elem, the histogram, the writer's
+// parameter record and its report are direct_count.h's, which brings lookup_kernels.h (count_found, from_count, Report, EMPTY).
 #pragma once
-#include "lookup_kernels.h"
+#include "direct_count.h"
 
 namespace msrg {
 
-static constexpr int NT = 256, LNT = 1024, MAXSPECS = 64, MAXSETS = 64;
-static constexpr int FLUSH_ROUNDS = 63;                   // 63 * 1024 = 64 512 counted rows between two flushes of the packed counters
+static constexpr int NT = msdc::NT, LNT = msdc::LNT, MAXSPECS = 64, MAXSETS = 64;
+static constexpr int FLUSH_ROUNDS = msdc::FLUSH_ADDS;     // a row is one add: the rounds of a workgroup between two flushes of the packed counters
 static_assert(FLUSH_ROUNDS * LNT <= 65535, "a 16-bit counter must not wrap between two flushes");
 
 using mstab::mask_holds;
@@ -34,16 +35,7 @@ struct Spec {
     uint32_t dst0, nlimbs, bits;
     int32_t mask_kind;
 };
-struct LimbReport { uint64_t overflow, first_overflow_row; uint32_t first_overflow_spec, pad; uint64_t active; };
-struct LimbParams {
-    const Spec* specs;                        // [gridDim.y], device memory
-    uint64_t* const* base;                    // the caller's pointer table, device memory
-    uint64_t* overflow;                       // zero before limb_decompose
-    uint64_t* active;                         // zero
-    uint64_t* first;                          // min over the overflowing rows of (spec << 32 | row); all ones
-    LimbReport* report;
-    size_t n;
-};
+using LimbParams = msdc::WriterParams<Spec>;
 
 template <int V> struct Row { uint64_t w[V]; bool active; };
 
@@ -75,55 +67,6 @@ __device__ __forceinline__ uint32_t limb_at(const uint64_t* w, unsigned pos, uns
     return (uint32_t)(x & ((1ull << bits) - 1));
 }
 
-// is w >> total != 0?  total <= 64 V
-template <int V>
-__device__ __forceinline__ bool above(const uint64_t* w, unsigned total) {
-    uint64_t any = 0;
-    #pragma unroll
-    for (int l = 0; l < V; l++) {
-        const unsigned lo = 64u * l;
-        if (total <= lo) any |= w[l];
-        else if (total < lo + 64) any |= w[l] >> (total - lo);
-    }
-    return any != 0;
-}
-
-// a limb x < 2^32 in Montgomery form.  Goldilocks: x * 2^64 = x * (2^32 - 1) (mod p), which is below 2^64 -- no general product.
-template <class F> __device__ __forceinline__ typename F::T limb_elem(uint32_t x);
-template <> __device__ __forceinline__ uint64_t limb_elem<msstage::FpT>(uint32_t x) { return gl::canon(((uint64_t)x << 32) - x); }
-template <> __device__ __forceinline__ f252::E limb_elem<msstage::Fp252T>(uint32_t x) { return f252::to_mont(f252::E{{(uint64_t)x, 0, 0, 0}}); }
-
-// two sums and a minimum of one value per lane -> one add / amin per workgroup, through the wave and LDS; every thread of the workgroup
-// calls it.  (join_kernels.h has the same reduction, beside a kernel that is not a template: that header belongs to one unit.)
-__device__ __forceinline__ void block_totals(uint64_t a, uint64_t b, uint64_t lo, uint64_t* sum_a, uint64_t* sum_b, uint64_t* min_lo) {
-    __shared__ uint64_t s_q[3];
-    if (threadIdx.x == 0) { s_q[0] = 0; s_q[1] = 0; s_q[2] = ~0ull; }
-    __syncthreads();
-#ifndef MS_EMU
-    #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        a += (uint64_t)__shfl_xor((unsigned long long)a, d);
-        b += (uint64_t)__shfl_xor((unsigned long long)b, d);
-        const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)lo, d);
-        lo = lo < o ? lo : o;
-    }
-    const bool speaker = (threadIdx.x & 63u) == 0;
-#else
-    const bool speaker = true;                                                 // the simulator has no wave: every lane speaks for itself
-#endif
-    if (speaker) {
-        if (a) add(&s_q[0], a);
-        if (b) add(&s_q[1], b);
-        if (lo != ~0ull) amin(&s_q[2], lo);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (s_q[0]) add(sum_a, s_q[0]);
-        if (s_q[1]) add(sum_b, s_q[1]);
-        if (s_q[2] != ~0ull) amin(min_lo, s_q[2]);
-    }
-}
-
 // grid (blocks, specs)
 template <class F>
 __global__ void __launch_bounds__(NT) limb_decompose(LimbParams P) {
@@ -131,37 +74,25 @@ __global__ void __launch_bounds__(NT) limb_decompose(LimbParams P) {
     const Spec S = P.specs[blockIdx.y];
     uint64_t* const* dst = P.base + S.dst0;
     const size_t stride = (size_t)gridDim.x * NT;
-    uint64_t nactive = 0, noverflow = 0, first = ~0ull;
+    uint64_t nactive = 0, noverflow = 0;
+    mstab::FirstRow first{~0ull};
     size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
     Row<V> cur = load_row<V>(S, i, P.n);
     while (i < P.n) {
         const Row<V> next = load_row<V>(S, i + stride, P.n);                 // in flight while this row's limbs go out
         if (cur.active) {
             nactive++;
-            if (above<V>(cur.w, S.nlimbs * S.bits)) {
-                noverflow++;
-                const uint64_t at = (uint64_t)blockIdx.y << 32 | (uint64_t)i;
-                if (at < first) first = at;
-            }
+            if (msdc::above<V>(cur.w, S.nlimbs * S.bits)) { noverflow++; first.see(blockIdx.y, i); }
         }
         for (unsigned j = 0; j < S.nlimbs; j++)                                // an inactive row's words are zero, and so are its limbs
-            F::store(dst[j], i, limb_elem<F>(limb_at<V>(cur.w, j * S.bits, S.bits)));
+            F::store(dst[j], i, msdc::limb_elem<F>(limb_at<V>(cur.w, j * S.bits, S.bits)));
         cur = next;
         i += stride;
     }
-    block_totals(nactive, noverflow, first, P.active, P.overflow, P.first);
+    mstab::block_totals(nactive, noverflow, first.at, P.active, P.overflow, P.first);
 }
 
-__global__ void limb_finish(LimbParams P) {
-    const uint64_t overflow = *P.overflow, first = *P.first;
-    LimbReport r;
-    r.overflow = overflow;
-    r.first_overflow_row = overflow ? (first & 0xFFFFFFFFull) : 0;
-    r.first_overflow_spec = overflow ? (uint32_t)(first >> 32) : 0;
-    r.pad = 0;
-    r.active = *P.active;
-    *P.report = r;
-}
+static __global__ void limb_finish(LimbParams P) { msdc::write_limb_report(P); }
 
 // ---- counts -------------------------------------------------------------------------------------------------------------------------
 struct Set {
@@ -195,48 +126,27 @@ __device__ __forceinline__ uint32_t bin_of(const uint64_t* col, size_t i, unsign
 template <int V>
 __global__ void __launch_bounds__(NT) range_count_plain(CountParams P) {
     const Set& L = P.sets[blockIdx.y];
-    uint64_t missing = 0, first = ~0ull;
+    uint64_t missing = 0;
+    mstab::FirstRow first{~0ull};
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < P.n; i += (size_t)gridDim.x * NT) {
         uint32_t found = mslk::EMPTY;
         if (mask_holds<V>(L.mask, L.mask_kind, i)) {
             found = bin_of<V>(L.col, i, P.bits);
-            if (found == mslk::EMPTY) {
-                missing++;
-                const uint64_t at = (uint64_t)blockIdx.y << 32 | (uint64_t)i;
-                if (at < first) first = at;
-            }
+            if (found == mslk::EMPTY) { missing++; first.see(blockIdx.y, i); }
         }
         mslk::count_found<true>(P.cnt, found);
     }
-    if (missing) { add(P.missing, missing); amin(P.first, first); }
-}
-
-// the workgroup's histogram -> the global counters: one add per non-zero bin; the histogram is zero again afterwards.  Every lane calls it.
-template <int HB>
-__device__ __forceinline__ void flush_bins(uint32_t* hist, uint32_t* cnt, unsigned nwords) {
-    __syncthreads();
-    for (unsigned k = threadIdx.x; k < nwords; k += LNT) {
-        const uint32_t w = hist[k];
-        if (w == 0) continue;
-        hist[k] = 0;
-        if (HB <= 15) add(cnt + k, w);
-        else {
-            if (w & 0xFFFFu) add(cnt + 2 * k, w & 0xFFFFu);
-            if (w >> 16) add(cnt + 2 * k + 1, w >> 16);
-        }
-    }
-    __syncthreads();
+    if (missing) { add(P.missing, missing); amin(P.first, first.at); }
 }
 
 // grid (G): workgroup b takes rows b * LNT + lane, + G * LNT, ... of every set.  bits <= HB.
 template <int V, int HB>
 __global__ void __launch_bounds__(LNT) range_count_lds(CountParams P) {
-    constexpr unsigned WORDS = HB <= 15 ? 1u << HB : 1u << 15;
-    __shared__ uint32_t hist[WORDS];
+    __shared__ uint32_t hist[msdc::hist_words<HB>];
     const unsigned nwords = HB <= 15 ? 1u << P.bits : 1u << 15;
-    for (unsigned k = threadIdx.x; k < nwords; k += LNT) hist[k] = 0;
-    __syncthreads();
-    uint64_t missing = 0, first = ~0ull;
+    msdc::hist_clear(hist, nwords);
+    uint64_t missing = 0;
+    mstab::FirstRow first{~0ull};
     int rounds = 0;
     for (unsigned s = 0; s < P.nsets; s++) {
         const Set& L = P.sets[s];
@@ -245,19 +155,14 @@ __global__ void __launch_bounds__(LNT) range_count_lds(CountParams P) {
             const size_t i = row0 + threadIdx.x;
             if (i < P.n && mask_holds<V>(L.mask, L.mask_kind, i)) {
                 const uint32_t v = bin_of<V>(L.col, i, P.bits);
-                if (v == mslk::EMPTY) {
-                    missing++;
-                    const uint64_t at = (uint64_t)s << 32 | (uint64_t)i;
-                    if (at < first) first = at;
-                }
-                else if (HB <= 15) add(hist + v, 1u);
-                else add(hist + (v >> 1), 1u << (16 * (v & 1u)));
+                if (v == mslk::EMPTY) { missing++; first.see(s, i); }
+                else msdc::hist_add<HB>(hist, v);
             }
-            if (HB > 15 && ++rounds == FLUSH_ROUNDS) { flush_bins<HB>(hist, P.cnt, nwords); rounds = 0; }
+            if (HB > 15 && ++rounds == FLUSH_ROUNDS) { msdc::flush_bins<HB>(hist, P.cnt, nwords); rounds = 0; }
         }
     }
-    flush_bins<HB>(hist, P.cnt, nwords);
-    if (missing) { add(P.missing, missing); amin(P.first, first); }
+    msdc::flush_bins<HB>(hist, P.cnt, nwords);
+    if (missing) { add(P.missing, missing); amin(P.first, first.at); }
 }
 
 template <class F>
@@ -265,16 +170,7 @@ __global__ void __launch_bounds__(NT) range_finish(CountParams P) {
     const size_t bins = (size_t)1 << P.bits;
     for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < P.n_m; j += (size_t)gridDim.x * NT)
         F::store(P.m, j, mslk::from_count<F>(j < bins ? P.cnt[j] : 0u));
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const uint64_t missing = *P.missing, first = *P.first;
-        mslk::Report r;
-        r.missing = missing;
-        r.first_missing_row = missing ? (first & 0xFFFFFFFFull) : 0;
-        r.first_missing_set = missing ? (uint32_t)(first >> 32) : 0;
-        r.pad = 0;
-        r.duplicate_table_rows = 0;
-        *P.report = r;
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) mslk::write_report(P.report, *P.missing, *P.first, 0);
 }
 
 }  // namespace msrg

@@ -1,8 +1,11 @@
-// What the kernels of the trace-table entry points share (ext_kernels.h, logup_kernels.h, lookup_kernels.h, sort_kernels.h, gap_kernels.h):
+// What the kernels of the trace-table entry points share (ext_kernels.h, logup_kernels.h, lookup_kernels.h, sort_kernels.h, gap_kernels.h,
+// join_kernels.h, direct_count.h):
 //   the activity mask   MASK_* and mask_holds: is a row active under (kind, mask column)?  ms_ext.cpp ties the kinds to MS_EXT_*.
 //   Canon<V>            the canonical integer of a Montgomery element, least significant word first
 //   integer atomics     add / amin / amax / aor / aand / cas / peek: the HIP atomics in the product; under MS_EMU plain read-modify-write,
 //                       which is exact there (the simulator runs the lanes of a launch one after another and its header has no 32-bit atomics)
+//   FirstRow            the smallest (group << 32 | row) seen -- a report's first missing or overflowing row -- and its decode
+//   block_totals        two sums and a minimum of one value per lane -> one add / amin per workgroup
 //   block_exclusive     the exclusive prefix of one value per thread of a workgroup, through LDS
 //   prefix_in_rounds    the exclusive prefix of an array longer than the workgroup, in place: rounds of one value per thread with a carry
 // Everything is inlined into the kernels that use it, which keep their own namespaces and names.
@@ -59,6 +62,46 @@ static __device__ __forceinline__ void aand(uint64_t* p, uint64_t v) { atomicAnd
 // a slot while other lanes insert: a relaxed load that the compiler neither caches in a register nor serves from the CU's own cache
 static __device__ __forceinline__ uint32_t peek(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #endif
+
+// The first row, in (group, row) order, that a report complains of: a lane keeps the smallest it sees, device memory takes the amin over
+// the lanes (all ones before the kernel), the finish kernel decodes.  A group is a lookup set or a spec; rows are below 2^32.
+struct FirstRow {
+    uint64_t at;                                                               // group << 32 | row; all ones: none seen
+    __device__ __forceinline__ void see(uint64_t group, uint64_t row) { const uint64_t v = group << 32 | row; if (v < at) at = v; }
+    __device__ __forceinline__ uint64_t row() const { return at == ~0ull ? 0 : at & 0xFFFFFFFFull; }
+    __device__ __forceinline__ uint32_t group() const { return at == ~0ull ? 0 : (uint32_t)(at >> 32); }
+};
+
+// two sums and a minimum of one value per lane -> one add / amin per workgroup, through the wave and LDS; every thread of the workgroup
+// calls it.  sum_b and min_lo may be null: nothing is added there.
+__device__ __forceinline__ void block_totals(uint64_t a, uint64_t b, uint64_t lo, uint64_t* sum_a, uint64_t* sum_b, uint64_t* min_lo) {
+    __shared__ uint64_t s_q[3];
+    if (threadIdx.x == 0) { s_q[0] = 0; s_q[1] = 0; s_q[2] = ~0ull; }
+    __syncthreads();
+#ifndef MS_EMU
+    #pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        a += (uint64_t)__shfl_xor((unsigned long long)a, d);
+        b += (uint64_t)__shfl_xor((unsigned long long)b, d);
+        const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)lo, d);
+        lo = lo < o ? lo : o;
+    }
+    const bool speaker = (threadIdx.x & 63u) == 0;
+#else
+    const bool speaker = true;                                                 // the simulator has no wave: every lane speaks for itself
+#endif
+    if (speaker) {
+        if (a) add(&s_q[0], a);
+        if (b) add(&s_q[1], b);
+        if (lo != ~0ull) amin(&s_q[2], lo);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_q[0]) add(sum_a, s_q[0]);
+        if (sum_b && s_q[1]) add(sum_b, s_q[1]);
+        if (min_lo && s_q[2] != ~0ull) amin(min_lo, s_q[2]);
+    }
+}
 
 // exclusive prefix over the `width` values v of a workgroup (one per thread; width = its thread count), through LDS; every thread calls it
 template <class T>

@@ -601,26 +601,53 @@ class RangeReport(LookupReport):
         return self
 
 
+def _write_spec_columns(who, planner, trace, specs, max_specs, record, refuse):
+    """What limb_decompose and bitwise_columns share: the trace's columns and field, the limit on the specs, refuse(spec, field) -> why the
+    field does not take the spec (or None), the specs as `record`s, the report buffer, the call ms_<who> -> (report buffer, columns, specs)"""
+    cols = trace.columns if isinstance(trace, Matrix) else list(trace)
+    specs = list(specs)
+    n, field = _same_columns(who, cols)
+    if field not in (GOLDILOCKS_FP, STARK252_FP):
+        raise ValueError(f"{who}: the trace is over Fp or Fp252")
+    if len(specs) > max_specs:
+        raise ValueError(f"{who}: at most {max_specs} specs in one call, not {len(specs)}")
+    for k, sp in enumerate(specs):
+        why = refuse(sp, field)
+        if why:
+            raise ValueError(f"{who}: spec {k}: {why}")
+    buf = GpuVec(planner, ctypes.sizeof(LimbReportRecord) // 8, GOLDILOCKS_FP)
+    rec = np.array([sp._record() for sp in specs], dtype=np.int32).reshape(-1, 8)
+    assert rec.nbytes == len(specs) * ctypes.sizeof(record)
+    L = planner.lib
+    L.check(getattr(L, "ms_" + who)(planner.handle, field, n, _ptr_array(cols), len(cols), rec.ctypes.data if rec.size else None, len(specs), buf.ptr))
+    return buf, cols, specs
+
+
+def _multiplicity_buffers(who, planner, n, field, T, rows, sets, record, out, n_m):
+    """What range_multiplicities and bitwise_multiplicities share: n_m (default: the length of `out`, or n) against the table's T rows
+    (`rows` in the refusal's words), the column m, the report buffer, the sets as `record`s -> (n_m, m, report buffer, records, their address)"""
+    if n_m is None:
+        n_m = len(out) if out is not None else n
+    n_m = int(n_m)
+    if n_m < T:
+        raise ValueError(f"{who}: m holds {n_m} elements, fewer than the {rows} rows of the table")
+    m = GpuVec(planner, n_m, field) if out is None else out
+    if len(m) < n_m or m.field != field:
+        raise ValueError(f"{who}: `out` is a column of the base field of at least n_m elements")
+    buf = GpuVec(planner, ctypes.sizeof(LookupReportRecord) // 8, GOLDILOCKS_FP)
+    rec = np.array([s._record() for s in sets], dtype=np.int32).reshape(-1, ctypes.sizeof(record) // 4)
+    assert rec.nbytes == len(sets) * ctypes.sizeof(record)
+    return n_m, m, buf, rec, rec.ctypes.data if rec.size else None
+
+
 def limb_decompose(planner, trace, specs):
     """Writes the limb columns of every LimbSpec into `trace` (a Matrix or a list of GpuVecs of one length and field) -> a LimbReport.
     The destination columns of a spec are columns of the trace that no spec reads (as source or mask) and no other spec writes.
     Enqueues and returns: no host wait until the report is read."""
-    cols = trace.columns if isinstance(trace, Matrix) else list(trace)
-    specs = list(specs)
-    n, field = _same_columns("limb_decompose", cols)
-    if field not in (GOLDILOCKS_FP, STARK252_FP):
-        raise ValueError("limb_decompose: the trace is over Fp or Fp252")
-    if len(specs) > RANGE_MAX_SPECS:
-        raise ValueError(f"limb_decompose: at most {RANGE_MAX_SPECS} specs in one call, not {len(specs)}")
-    for k, sp in enumerate(specs):
+    def too_wide(sp, field):
         if sp.nlimbs * sp.bits > 64 * FIELD_WORDS[field]:
-            raise ValueError(f"limb_decompose: spec {k}: {sp.nlimbs} limbs of {sp.bits} bits are more than the {64 * FIELD_WORDS[field]} bits of an element's words")
-    buf = GpuVec(planner, ctypes.sizeof(LimbReportRecord) // 8, GOLDILOCKS_FP)
-    rec = np.array([sp._record() for sp in specs], dtype=np.int32).reshape(-1, 8)
-    assert rec.nbytes == len(specs) * ctypes.sizeof(LimbSpecRecord)
-    L = planner.lib
-    L.check(L.ms_limb_decompose(planner.handle, field, n, _ptr_array(cols), len(cols), rec.ctypes.data if rec.size else None, len(specs), buf.ptr))
-    return LimbReport(planner, buf, cols, specs)
+            return f"{sp.nlimbs} limbs of {sp.bits} bits are more than the {64 * FIELD_WORDS[field]} bits of an element's words"
+    return LimbReport(planner, *_write_spec_columns("limb_decompose", planner, trace, specs, RANGE_MAX_SPECS, LimbSpecRecord, too_wide))
 
 
 def range_multiplicities(planner, trace, bits, sets, out=None, n_m=None):
@@ -635,20 +662,9 @@ def range_multiplicities(planner, trace, bits, sets, out=None, n_m=None):
         raise ValueError(f"range_multiplicities: bits is 1 .. {RANGE_MAX_TABLE_BITS}, not {bits}")
     if len(sets) > RANGE_MAX_SETS:
         raise ValueError(f"range_multiplicities: at most {RANGE_MAX_SETS} sets in one call, not {len(sets)}")
-    if n_m is None:
-        n_m = len(out) if out is not None else n
-    n_m = int(n_m)
-    if n_m < (1 << bits):
-        raise ValueError(f"range_multiplicities: m holds {n_m} elements, fewer than the 2^{bits} rows of the table")
-    m = GpuVec(planner, n_m, field) if out is None else out
-    if len(m) < n_m or m.field != field:
-        raise ValueError("range_multiplicities: `out` is a column of the base field of at least n_m elements")
-    buf = GpuVec(planner, ctypes.sizeof(LookupReportRecord) // 8, GOLDILOCKS_FP)
-    rec = np.array([s._record() for s in sets], dtype=np.int32).reshape(-1, 4)
-    assert rec.nbytes == len(sets) * ctypes.sizeof(RangeSetRecord)
+    n_m, m, buf, rec, h_sets = _multiplicity_buffers("range_multiplicities", planner, n, field, 1 << bits, f"2^{bits}", sets, RangeSetRecord, out, n_m)
     L = planner.lib
-    L.check(L.ms_range_multiplicities(planner.handle, field, n, _ptr_array(cols), len(cols), bits, rec.ctypes.data if rec.size else None, len(sets),
-                                      n_m, m.ptr, buf.ptr))
+    L.check(L.ms_range_multiplicities(planner.handle, field, n, _ptr_array(cols), len(cols), bits, h_sets, len(sets), n_m, m.ptr, buf.ptr))
     return m, RangeReport(planner, buf, cols, sets, bits)
 
 
@@ -759,22 +775,10 @@ def bitwise_columns(planner, trace, specs):
     (its overflow: active rows with an operand that does not fit `width` bits; their low bits still go into the result).  The dst of a spec
     is a column of the trace that no spec reads (as operand or mask) and no other spec writes.  Enqueues and returns: no host wait until the
     report is read."""
-    cols = trace.columns if isinstance(trace, Matrix) else list(trace)
-    specs = list(specs)
-    n, field = _same_columns("bitwise_columns", cols)
-    if field not in BITWISE_WMAX:
-        raise ValueError("bitwise_columns: the trace is over Fp or Fp252")
-    if len(specs) > BITWISE_MAX_SPECS:
-        raise ValueError(f"bitwise_columns: at most {BITWISE_MAX_SPECS} specs in one call, not {len(specs)}")
-    for k, sp in enumerate(specs):
+    def too_wide(sp, field):
         if sp.width > BITWISE_WMAX[field]:
-            raise ValueError(f"bitwise_columns: spec {k}: an operand of this field has 1 .. {BITWISE_WMAX[field]} bits, not {sp.width}")
-    buf = GpuVec(planner, ctypes.sizeof(LimbReportRecord) // 8, GOLDILOCKS_FP)
-    rec = np.array([sp._record() for sp in specs], dtype=np.int32).reshape(-1, 8)
-    assert rec.nbytes == len(specs) * ctypes.sizeof(BitwiseSpecRecord)
-    L = planner.lib
-    L.check(L.ms_bitwise_columns(planner.handle, field, n, _ptr_array(cols), len(cols), rec.ctypes.data if rec.size else None, len(specs), buf.ptr))
-    return BitwiseColumnsReport(planner, buf, cols, specs)
+            return f"an operand of this field has 1 .. {BITWISE_WMAX[field]} bits, not {sp.width}"
+    return BitwiseColumnsReport(planner, *_write_spec_columns("bitwise_columns", planner, trace, specs, BITWISE_MAX_SPECS, BitwiseSpecRecord, too_wide))
 
 
 def _bitwise_ops(who, bits, ops):
@@ -836,20 +840,10 @@ def bitwise_multiplicities(planner, trace, bits, ops, sets, out=None, n_m=None):
             raise ValueError(f"bitwise_multiplicities: set {s}: its op is not one of the table's ops")
         if st.nlimbs * bits > BITWISE_WMAX[field]:
             raise ValueError(f"bitwise_multiplicities: set {s}: {st.nlimbs} limbs of {bits} bits are more than the {BITWISE_WMAX[field]} bits an operand may have")
-    if n_m is None:
-        n_m = len(out) if out is not None else n
-    n_m = int(n_m)
-    if n_m < T:
-        raise ValueError(f"bitwise_multiplicities: m holds {n_m} elements, fewer than the {T} rows of the table")
-    m = GpuVec(planner, n_m, field) if out is None else out
-    if len(m) < n_m or m.field != field:
-        raise ValueError("bitwise_multiplicities: `out` is a column of the base field of at least n_m elements")
-    buf = GpuVec(planner, ctypes.sizeof(LookupReportRecord) // 8, GOLDILOCKS_FP)
-    rec = np.array([s._record() for s in sets], dtype=np.int32).reshape(-1, 8)
-    assert rec.nbytes == len(sets) * ctypes.sizeof(BitwiseSetRecord)
+    n_m, m, buf, rec, h_sets = _multiplicity_buffers("bitwise_multiplicities", planner, n, field, T, T, sets, BitwiseSetRecord, out, n_m)
     L = planner.lib
-    L.check(L.ms_bitwise_multiplicities(planner.handle, field, n, _ptr_array(cols), len(cols), bits, codes.ctypes.data, len(codes),
-                                        rec.ctypes.data if rec.size else None, len(sets), n_m, m.ptr, buf.ptr))
+    L.check(L.ms_bitwise_multiplicities(planner.handle, field, n, _ptr_array(cols), len(cols), bits, codes.ctypes.data, len(codes), h_sets, len(sets),
+                                        n_m, m.ptr, buf.ptr))
     return m, BitwiseReport(planner, buf, cols, sets, bits)
 
 

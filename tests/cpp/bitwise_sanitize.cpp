@@ -1,4 +1,4 @@
-// Host code and kernels of the bitwise-operation columns (ministark_amd/csrc/ms_bitwise.cpp, bitwise_kernels.h) under AddressSanitizer and
+// Host code and kernels of the bitwise-operation columns (ministark_amd/csrc/ms_bitwise.cpp and count_args.h; bitwise_kernels.h on direct_count.h) under AddressSanitizer and
 // UBSan, as a stand-alone CPU program: its own main, linked with the simulator build of the library's sources, where device memory is
 // malloc'd memory and a result column, a bin or a histogram word out of range is a heap (or global) overflow the sanitizer sees.  It runs
 // ms_bitwise_columns over lengths 0 .. 1025, widths from 1 to WMAX, the three ops, both fields and the three masks; ms_bitwise_table for

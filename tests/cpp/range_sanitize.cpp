@@ -1,4 +1,4 @@
-// Host code and kernels of the range check (ministark_amd/csrc/ms_range.cpp, range_kernels.h) under AddressSanitizer and UBSan, as a
+// Host code and kernels of the range check (ministark_amd/csrc/ms_range.cpp and count_args.h; range_kernels.h on direct_count.h) under AddressSanitizer and UBSan, as a
 // stand-alone CPU program: its own main, linked with the simulator build of the library's sources, where device memory is malloc'd memory
 // and a limb column, a bin or a histogram word out of range is a heap (or global) overflow the sanitizer sees.  It runs ms_limb_decompose
 // over lengths 0 .. 1025, every (bits, nlimbs) of tests/test_limb_decompose.py, both fields and the three masks, and

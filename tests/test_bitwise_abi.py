@@ -69,7 +69,7 @@ def test_the_records_are_the_headers():
     assert [m for _, m in _members("ms_bitwise_spec")] == ["op", "a", "b", "dst", "width", "mask", "mask_col", "pad"]
     assert [m for _, m in _members("ms_bitwise_set")] == ["op", "a", "b", "c", "nlimbs", "mask", "mask_col", "pad"]
     host = open(os.path.join(ROOT, "ministark_amd", "csrc", "ms_bitwise.cpp")).read()
-    assert "sizeof(ms_bitwise_spec) == 32 && sizeof(ms_bitwise_set) == 32" in host and "sizeof(msrg::LimbReport) == sizeof(ms_limb_report)" in host
+    assert "sizeof(ms_bitwise_spec) == 32 && sizeof(ms_bitwise_set) == 32" in host and "sizeof(msdc::LimbReport) == sizeof(ms_limb_report)" in host
 
 
 def test_the_python_constants_are_the_headers():
@@ -90,20 +90,27 @@ def test_the_kernels_take_their_atomics_and_their_helpers_from_the_layers_below(
     csrc = os.path.join(ROOT, "ministark_amd", "csrc")
     kernels = open(os.path.join(csrc, "bitwise_kernels.h")).read()
     code = re.sub(r"//.*", "", kernels)
-    assert '#include "range_kernels.h"' in kernels                              # which brings lookup_kernels.h and table_common.h
+    assert '#include "direct_count.h"' in kernels and kernels.count("#include") == 1      # which brings lookup_kernels.h, which brings table_common.h
+    assert '"range_kernels.h"' not in code and "msrg" not in code and "#define" not in code      # the sibling unit's header is not this one's layer below
     for fn in ("add", "amin"):
         assert "using mstab::%s;" % fn in kernels
     assert "atomic" not in code                                                 # every atomic goes through table_common.h, which the simulator makes exact
     assert "mslk::count_found<true>" in code and "mslk::from_count<F>" in code and "mstab::Canon<V>::words" in code
-    assert "msrg::flush_bins<HB>" in code and "msrg::block_totals" in code and "msrg::above<V>" in code and "msrg::limb_elem<F>" in code
+    assert "msdc::flush_bins<HB>" in code and "msdc::hist_add<HB>" in code and "msdc::hist_clear(" in code and "msdc::above<V>" in code and "msdc::limb_elem<F>" in code
+    assert "mstab::block_totals(" in code and "mstab::FirstRow" in code and "mslk::write_report(" in code and "msdc::write_limb_report(" in code
+    for helper in ("flush_bins", "hist_add", "hist_clear", "above", "limb_elem", "block_totals", "write_report", "write_limb_report", "count_found", "from_count"):
+        assert not re.search(r"__forceinline__ [\w:<> ]+ %s\(" % helper, code), helper      # taken from below (tests/test_range_abi.py: defined once), not restated
     assert "extern __shared__" not in code                                      # static shared memory only: the simulator has no dynamic kind
-    assert "static_assert(FLUSH_INCS * LNT <= 65535" in code and "static_assert(PACKED_MAX_LIMBS <= FLUSH_INCS" in code
+    assert "static_assert(FLUSH_INCS * LNT <= 65535" in code and "static_assert(PACKED_MAX_LIMBS <= FLUSH_INCS" in code and "FLUSH_INCS = msdc::FLUSH_ADDS;" in code
     host = open(os.path.join(csrc, "ms_bitwise.cpp")).read()
     assert "static_assert(msbw::MAXSPECS == (int)MS_BITWISE_MAX_SPECS && msbw::MAXSETS == (int)MS_BITWISE_MAX_SETS" in host
-    assert 'getenv("MS_BITWISE_FORM")' in host
-    for lower in ("range_kernels.h", "lookup_kernels.h"):
-        text = open(os.path.join(csrc, lower)).read()
-        assert "msbw" not in text and "bitwise" not in text.lower()             # the layers below do not know of this one
+    assert '"MS_BITWISE_FORM"' in host and "getenv(form_var)" in open(os.path.join(csrc, "count_args.h")).read()
+    text = open(os.path.join(csrc, "lookup_kernels.h")).read()
+    assert "msbw" not in text and "bitwise" not in text.lower()                 # the layers below do not know of this one
+    for lower in ("direct_count.h", "lookup_kernels.h", "table_common.h"):      # outside the comments that say who uses them
+        assert not re.search(r"msrg|msbw|range|bitwise", re.sub(r"//.*", "", open(os.path.join(csrc, lower)).read()).lower()), lower
+    sibling = open(os.path.join(csrc, "range_kernels.h")).read()
+    assert "msbw" not in sibling and "bitwise" not in sibling.lower()           # nor does the sibling unit
     build = __import__("ministark_amd.build", fromlist=["SOURCES"])
     assert "ms_bitwise.cpp" in build.SOURCES and HEADER in build._deps()
 

@@ -76,8 +76,9 @@ def test_the_kernels_are_the_lookup_layers_build_and_a_probe_of_their_own():
     kernels = open(os.path.join(csrc, "join_kernels.h")).read()
     assert '#include "lookup_kernels.h"' in kernels and "lookup_build" not in re.sub(r"//.*", "", kernels)      # reused, not restated
     assert "static constexpr uint32_t NONE = 0xFFFFFFFFu;" in kernels
-    for fn in ("add", "amin"):
+    for fn in ("add", "amin", "block_totals"):
         assert "using mstab::%s;" % fn in kernels
+    assert "void block_totals(" not in kernels and "mstab::FirstRow" in kernels  # the workgroup reduction and the first-row decode are table_common.h's
     assert "atomic" not in re.sub(r"//.*", "", kernels)                         # every atomic goes through table_common.h, which the simulator makes exact
     host = open(os.path.join(csrc, "ms_join.cpp")).read()
     assert "static_assert(mslk::MAXW == (int)MS_JOIN_MAX_WIDTH && mslk::MAXSETS == (int)MS_JOIN_MAX_SETS" in host

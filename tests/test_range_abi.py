@@ -85,18 +85,45 @@ def test_the_kernels_take_their_atomics_and_their_finish_from_the_layers_below()
     csrc = os.path.join(ROOT, "ministark_amd", "csrc")
     kernels = open(os.path.join(csrc, "range_kernels.h")).read()
     code = re.sub(r"//.*", "", kernels)
-    assert '#include "lookup_kernels.h"' in kernels                             # which brings table_common.h
+    assert '#include "direct_count.h"' in kernels and kernels.count("#include") == 1      # which brings lookup_kernels.h, which brings table_common.h
+    shared = open(os.path.join(csrc, "direct_count.h")).read()
+    shared_code = re.sub(r"//.*", "", shared)
+    assert '#include "lookup_kernels.h"' in shared and shared.count("#include") == 1 and "atomic" not in shared_code and "extern __shared__" not in shared_code
     for fn in ("add", "amin"):
         assert "using mstab::%s;" % fn in kernels
     assert "atomic" not in code                                                 # every atomic goes through table_common.h, which the simulator makes exact
     assert "mslk::count_found<true>" in code and "mslk::from_count<F>" in code and "mstab::Canon<V>::words" in code
     assert "extern __shared__" not in code                                      # static shared memory only: the simulator has no dynamic kind
-    assert "static_assert(FLUSH_ROUNDS * LNT <= 65535" in code
+    assert "msdc::flush_bins<HB>" in code and "msdc::hist_add<HB>" in code and "msdc::hist_clear(" in code and "msdc::above<V>" in code and "msdc::limb_elem<F>" in code
+    assert "mstab::block_totals(" in code and "mstab::FirstRow" in code and "mslk::write_report(" in code and "msdc::write_limb_report(" in code
+    assert "static_assert(FLUSH_ROUNDS * LNT <= 65535" in code and "FLUSH_ROUNDS = msdc::FLUSH_ADDS;" in code
+    assert "static_assert(FLUSH_ADDS * LNT <= 65535" in shared_code
+    # each helper comes from exactly one layer below: defined once under csrc/, and not here
+    texts = {f: re.sub(r"//.*", "", open(os.path.join(csrc, f)).read()) for f in os.listdir(csrc) if f.endswith((".h", ".cpp"))}
+    for helper, home in (("flush_bins", "direct_count.h"), ("hist_add", "direct_count.h"), ("hist_clear", "direct_count.h"), ("above", "direct_count.h"),
+                         ("limb_elem", "direct_count.h"), ("write_limb_report", "direct_count.h"), ("block_totals", "table_common.h"),
+                         ("write_report", "lookup_kernels.h"), ("count_found", "lookup_kernels.h"), ("from_count", "lookup_kernels.h")):
+        defined = [f for f, text in texts.items() if re.search(r"__forceinline__ [\w:<> ]+ %s\(" % helper, text)]
+        assert defined == [home], (helper, defined)
+    for record, home in (("FirstRow", "table_common.h"), ("LimbReport", "direct_count.h"), ("WriterParams", "direct_count.h")):
+        assert [f for f, text in texts.items() if re.search(r"struct %s\b" % record, text)] == [home], record
     host = open(os.path.join(csrc, "ms_range.cpp")).read()
     assert "static_assert(msrg::MAXSPECS == (int)MS_RANGE_MAX_SPECS && msrg::MAXSETS == (int)MS_RANGE_MAX_SETS" in host
-    assert 'getenv("MS_RANGE_FORM")' in host
+    assert '"MS_RANGE_FORM"' in host and "getenv(form_var)" in open(os.path.join(csrc, "count_args.h")).read()
     lookup = open(os.path.join(csrc, "lookup_kernels.h")).read()
     assert "msrg" not in lookup and "range" not in lookup.lower()               # the lookup layer does not know of this one
+    for lower in ("direct_count.h", "lookup_kernels.h", "table_common.h"):      # nor does any layer below, outside the comments that say who uses it
+        assert not re.search(r"msrg|msbw|range|bitwise", texts[lower].lower()), lower
+
+
+def test_a_shared_helper_is_defined_once_and_no_kernel_is_renamed_by_the_preprocessor():
+    csrc = os.path.join(ROOT, "ministark_amd", "csrc")
+    texts = {f: open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".h", ".cpp"))}
+    assert [f for f, text in texts.items() if re.search(r"\bvoid block_totals\(", text)] == ["table_common.h"]
+    kernels = {m.group(1) for text in texts.values() for m in re.finditer(r"__global__\s+void\s+(?:__launch_bounds__\([^\n]*?\)\s+)?(\w+)\s*\(", text)}
+    assert {"limb_finish", "limb_decompose", "range_count_lds", "bitwise_col_finish", "bitwise_count_lds", "join_finish", "lookup_finish"} <= kernels
+    defined = {m.group(1) for text in texts.values() for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)", text, flags=re.M)}
+    assert not kernels & defined, sorted(kernels & defined)
     build = __import__("ministark_amd.build", fromlist=["SOURCES"])
     assert "ms_range.cpp" in build.SOURCES and HEADER in build._deps()
 

@@ -1,13 +1,15 @@
-"""Every refusal of the seven trace-table entry points -- ms_build_extension_columns, ms_build_logup_columns, ms_lookup_multiplicities,
-ms_sort_rows, ms_permute_columns, ms_gap_plan, ms_gap_fill -- replayed through the C ABI against tests/golden/table_refusals.json: the
-same return code and the same ms_last_error text, word for word.  The file was recorded before the entry points came to share their
-argument checks (ms_internal.h: BaseColumns, canon_named; ext_args.h), so it pins what each one says and WHICH refusal wins where two
-could fire.  Null arguments, counts and indices out of range, bad kinds and signs, the size limits, every overlap pair, and the checked
+"""Every refusal of twelve trace-table entry points -- ms_build_extension_columns, ms_build_logup_columns, ms_lookup_multiplicities,
+ms_sort_rows, ms_permute_columns, ms_gap_plan, ms_gap_fill, ms_limb_decompose, ms_range_multiplicities, ms_bitwise_columns,
+ms_bitwise_table, ms_bitwise_multiplicities -- replayed through the C ABI against tests/golden/table_refusals.json: the same return
+code and the same ms_last_error text, word for word.  Each entry point's cases were recorded before it came to share its argument
+checks with the others (ms_internal.h: BaseColumns, canon_named; ext_args.h; count_args.h), so the file pins what each one says and
+WHICH refusal wins where two could fire.  Null arguments, counts and indices out of range, bad kinds and signs, the size limits, every overlap pair, and the checked
 mode: a non-canonical element in a column the call names is refused, in one it does not name the call goes through (the two column
 builders scan the whole base table and refuse both).
 
 All buffers are slots of one small allocation (n = 8 rows; a size limit is refused before anything looks at a buffer), zero but for the
-index and the elements that are >= p.  A case that is not refused is recorded with code 0 and no text.
+index and the elements that are >= p.  A case that is not refused is recorded with code 0 and no text.  "env" in a case: environment
+variables set for the call (MS_RANGE_FORM, MS_BITWISE_FORM).
 
     python -m tests.test_table_refusals        records the file anew from the simulator build (only when a refusal is ADDED)"""
 import ctypes
@@ -146,6 +148,60 @@ def call_fill(e, ctx=True, field=FP, n_src=N, base=BASE, nbase=None, perm=PERM, 
     cols = None if cols is None else list(cols)
     return e.L.ms_gap_fill(e.h if ctx else None, field, n_src, e.table(base), len(base) if nbase is None else nbase, e.addr(perm), n, e.addr(start),
                            e.words(cols), e.table(dst), len(cols) if ncols is None else ncols, n_out)
+
+
+def limb(src=0, dst0=2, nlimbs=2, bits=4, mask=0, mask_col=0):
+    return [src, dst0, nlimbs, bits, mask, mask_col, 0, 0]
+
+
+def call_limb(e, ctx=True, field=FP, n=N, base=BASE, nbase=None, specs=(limb(),), nspecs=None, report=REPORT):
+    specs = None if specs is None else list(specs)
+    return e.L.ms_limb_decompose(e.h if ctx else None, field, n, e.table(base), len(base) if nbase is None else nbase,
+                                 e.words(specs), (len(specs) if specs else 0) if nspecs is None else nspecs, e.addr(report))
+
+
+def rset(col=0, mask=0, mask_col=0):
+    return [col, mask, mask_col, 0]
+
+
+def call_range(e, ctx=True, field=FP, n=N, base=BASE, nbase=None, bits=3, sets=(rset(), rset(1)), nsets=None, n_m=N, m=OUT[0], report=REPORT):
+    sets = None if sets is None else list(sets)
+    return e.L.ms_range_multiplicities(e.h if ctx else None, field, n, e.table(base), len(base) if nbase is None else nbase, bits,
+                                       e.words(sets), (len(sets) if sets else 0) if nsets is None else nsets, n_m, e.addr(m), e.addr(report))
+
+
+AND, OR, XOR = 0, 1, 2
+
+
+def bspec(op=AND, a=0, b=1, dst=2, width=8, mask=0, mask_col=0):
+    return [op, a, b, dst, width, mask, mask_col, 0]
+
+
+def call_bcols(e, ctx=True, field=FP, n=N, base=BASE, nbase=None, specs=(bspec(),), nspecs=None, report=REPORT):
+    specs = None if specs is None else list(specs)
+    return e.L.ms_bitwise_columns(e.h if ctx else None, field, n, e.table(base), len(base) if nbase is None else nbase,
+                                  e.words(specs), (len(specs) if specs else 0) if nspecs is None else nspecs, e.addr(report))
+
+
+# the table of 3 ops over pairs of 1-bit limbs has 12 rows: a column of it over Fp252 is a slot and a half
+TOP, TX, TY, TZ = S(16), S(18), S(20), S(22)
+
+
+def call_btable(e, ctx=True, field=FP, bits=1, ops=(AND, OR, XOR), nops=None, n_t=12, top=TOP, tx=TX, ty=TY, tz=TZ):
+    return e.L.ms_bitwise_table(e.h if ctx else None, field, bits, e.words(None if ops is None else list(ops)), (len(ops) if ops else 0) if nops is None else nops,
+                                n_t, e.addr(top), e.addr(tx), e.addr(ty), e.addr(tz))
+
+
+def bset(op=AND, a=0, b=1, c=NONE, nlimbs=2, mask=0, mask_col=0):
+    return [op, a, b, c, nlimbs, mask, mask_col, 0]
+
+
+def call_bmult(e, ctx=True, field=FP, n=N, base=BASE, nbase=None, bits=1, ops=(AND, XOR), nops=None, sets=(bset(), bset(XOR, c=2)), nsets=None, n_m=N,
+               m=OUT[0], report=REPORT):
+    sets = None if sets is None else list(sets)
+    return e.L.ms_bitwise_multiplicities(e.h if ctx else None, field, n, e.table(base), len(base) if nbase is None else nbase, bits,
+                                         e.words(None if ops is None else list(ops)), (len(ops) if ops else 0) if nops is None else nops,
+                                         e.words(sets), (len(sets) if sets else 0) if nsets is None else nsets, n_m, e.addr(m), e.addr(report))
 
 
 BIG30, BIG32 = (1 << 30) + 1, (1 << 32) + 1
@@ -443,6 +499,323 @@ ENTRIES = {
         ("checked: fp252", dict(checked=True, field=F252, base=[BAD_252, S(1), S(2), S(3)])),
         ("checked: n_out 0", dict(checked=True, n_out=0, base=[BAD_FP, S(1), S(2), S(3)])),
     ]),
+    "ms_limb_decompose": (call_limb, [
+        ("accepted", {}),
+        ("accepted over fp252", dict(field=F252)),
+        ("null ctx", dict(ctx=False)),
+        ("null d_base", dict(base=None, nbase=4)),
+        ("null h_specs", dict(specs=None, nspecs=1)),
+        ("no specs", dict(specs=None)),
+        ("null d_report", dict(report=None)),
+        ("fq3", dict(field=FQ3)),
+        ("unknown field", dict(field=7)),
+        ("65 specs", dict(specs=[limb()] * 65)),
+        ("rows 2^32 + 1", dict(n=BIG32)),
+        ("rows 2^32 are not refused for their number", dict(n=1 << 32, specs=[limb(src=9)])),
+        ("null base column", dict(base=BASE_NULL2)),
+        ("source column 4", dict(specs=[limb(src=4)])),
+        ("source column -1", dict(specs=[limb(), limb(src=-1, dst0=1, nlimbs=1)])),
+        ("mask kind 3", dict(specs=[limb(mask=3)])),
+        ("mask kind -1", dict(specs=[limb(mask=-1)])),
+        ("mask column 4", dict(specs=[limb(mask=1, mask_col=4)])),
+        ("mask column -1", dict(specs=[limb(mask=2, mask_col=-1)])),
+        ("mask column ignored when always", dict(specs=[limb(mask=0, mask_col=99)])),
+        ("0 bits", dict(specs=[limb(bits=0)])),
+        ("33 bits", dict(specs=[limb(bits=33)])),
+        ("0 limbs", dict(specs=[limb(nlimbs=0)])),
+        ("257 limbs", dict(specs=[limb(nlimbs=257)])),
+        ("5 limbs of 16 bits over fp", dict(specs=[limb(nlimbs=5, bits=16)])),
+        ("9 limbs of 32 bits over fp252", dict(field=F252, specs=[limb(nlimbs=9, bits=32)])),
+        ("2 limbs of 32 bits over fp", dict(specs=[limb(nlimbs=2, bits=32)])),
+        ("destination -1", dict(specs=[limb(dst0=-1)])),
+        ("destination 4", dict(specs=[limb(dst0=4)])),
+        ("destinations past the table", dict(specs=[limb(dst0=3, nlimbs=2)])),
+        ("source before mask before bits before limbs before destination", dict(specs=[limb(src=9, mask=9, bits=0, nlimbs=0, dst0=9)])),
+        ("mask before bits before limbs before destination", dict(specs=[limb(mask=9, bits=0, nlimbs=0, dst0=9)])),
+        ("bits before limbs before destination", dict(specs=[limb(bits=0, nlimbs=0, dst0=9)])),
+        ("limbs before their width before destination", dict(specs=[limb(bits=32, nlimbs=300, dst0=9)])),
+        ("width before destination", dict(specs=[limb(bits=32, nlimbs=3, dst0=9)])),
+        ("rows before specs", dict(n=BIG32, specs=[limb(src=9)])),
+        ("count before null base column", dict(base=BASE_NULL2, specs=[limb()] * 65)),
+        ("destinations of two specs overlap", dict(specs=[limb(0, 2, 2), limb(1, 3, 1)])),
+        ("destinations of the first and third spec overlap", dict(specs=[limb(0, 1, 1, mask=0), limb(0, 2, 1), limb(0, 1, 3)])),
+        ("two destination columns in the same memory go through", dict(base=[S(0), S(1), S(2), S(2)])),
+        ("two specs' destinations in the same memory go through", dict(base=[S(0), S(1), S(2), S(2, 8)], specs=[limb(0, 2, 1), limb(1, 3, 1)])),
+        ("destination is the source", dict(specs=[limb(0, 0, 1)])),
+        ("destination is another spec's source", dict(specs=[limb(0, 2, 1), limb(2, 3, 1)])),
+        ("destination is a later spec's mask", dict(specs=[limb(0, 2, 2), limb(0, 1, 1, mask=1, mask_col=3)])),
+        ("destination and source memory overlap", dict(base=[S(0), S(1), S(0, 56), S(3)], specs=[limb(0, 2, 1)])),
+        ("second destination and mask memory overlap", dict(base=[S(0), S(1), S(2), S(1, 8)], specs=[limb(0, 2, 2, mask=1, mask_col=1)])),
+        ("destination and unnamed column memory overlap goes through", dict(base=[S(0), S(2), S(2), S(3)], specs=[limb(0, 2, 1)])),
+        ("d_report and source overlap", dict(report=S(0, 56))),
+        ("d_report and the mask's column overlap", dict(specs=[limb(mask=2, mask_col=1)], report=S(1))),
+        ("d_report and destination overlap", dict(report=S(3, 8))),
+        ("d_report in an unnamed column", dict(report=S(1))),
+        ("the first spec's source before the second's destinations", dict(specs=[limb(0, 0, 1), limb(1, 0, 1)])),
+        ("two specs' destinations before the second's source", dict(specs=[limb(0, 2, 1), limb(2, 2, 1)])),
+        ("destinations before d_report", dict(specs=[limb(0, 2, 1), limb(1, 2, 1)], report=S(0))),
+        ("a read column before a destination for d_report", dict(base=[S(0), S(1), S(2), S(2, 64)], specs=[limb(3, 2, 1)], report=S(2, 56))),
+        ("a later spec's destinations before d_report and the first's destination", dict(specs=[limb(0, 2, 1), limb(1, 2, 1)], report=S(2))),
+        ("n 0", dict(n=0)),
+        ("n 0 passes the memory overlaps", dict(n=0, base=[S(0), S(1), S(0), S(3)], report=S(0))),
+        ("n 0 still refuses a destination that is the source", dict(n=0, specs=[limb(0, 0, 1)])),
+        ("checked: source", dict(checked=True, base=[BAD_FP, S(1), S(2), S(3)])),
+        ("checked: the mask's column", dict(checked=True, base=[S(0), BAD_FP, S(2), S(3)], specs=[limb(mask=1, mask_col=1)])),
+        ("checked: unnamed column", dict(checked=True, base=[S(0), BAD_FP, S(2), S(3)])),
+        ("checked: destination", dict(checked=True, base=WITH_BAD)),
+        ("checked: fp252", dict(checked=True, field=F252, base=[BAD_252, S(1), S(2), S(3)])),
+        ("checked: overlap first", dict(checked=True, base=[BAD_FP, S(1), S(2), S(3)], report=S(2))),
+        ("checked: n 0", dict(checked=True, n=0, base=[BAD_FP, S(1), S(2), S(3)])),
+        ("checked: no specs", dict(checked=True, specs=None, base=[BAD_FP, S(1), S(2), S(3)])),
+    ]),
+    "ms_range_multiplicities": (call_range, [
+        ("accepted", {}),
+        ("accepted over fp252", dict(field=F252)),
+        ("null ctx", dict(ctx=False)),
+        ("null d_base", dict(base=None, nbase=4)),
+        ("null h_sets", dict(sets=None, nsets=1)),
+        ("no sets", dict(sets=None)),
+        ("null d_m", dict(m=None)),
+        ("null d_report", dict(report=None)),
+        ("fq3", dict(field=FQ3)),
+        ("unknown field", dict(field=7)),
+        ("0 bits", dict(bits=0)),
+        ("25 bits", dict(bits=25)),
+        ("65 sets", dict(sets=[rset()] * 65)),
+        ("d_m of 7", dict(n_m=7)),
+        ("d_m of 2^24 - 1 for 24 bits", dict(bits=24, n_m=(1 << 24) - 1)),
+        ("null base column", dict(base=BASE_NULL2)),
+        ("set column 4", dict(sets=[rset(), rset(4)])),
+        ("set column -1", dict(sets=[rset(-1)])),
+        ("mask kind 3", dict(sets=[rset(mask=3)])),
+        ("mask kind -1", dict(sets=[rset(), rset(mask=-1)])),
+        ("mask column 4", dict(sets=[rset(mask=1, mask_col=4)])),
+        ("mask column -1", dict(sets=[rset(mask=2, mask_col=-1)])),
+        ("column before mask", dict(sets=[rset(9, mask=9)])),
+        ("bits before sets before d_m before null base column", dict(base=BASE_NULL2, bits=0, sets=[rset()] * 65, n_m=0)),
+        ("sets before d_m before null base column", dict(base=BASE_NULL2, sets=[rset()] * 65, n_m=0)),
+        ("d_m before null base column", dict(base=BASE_NULL2, n_m=0)),
+        ("rows 2^32 + 1", dict(n=BIG32)),
+        ("2 sets of 2^31 rows", dict(n=1 << 31)),
+        ("1 set of 2^32 rows", dict(n=1 << 32, sets=[rset()])),
+        ("column before rows", dict(n=BIG32, sets=[rset(4)])),
+        ("rows before counters", dict(n=BIG32, sets=[rset()] * 64)),
+        ("d_m and named base overlap", dict(m=S(1, 8))),
+        ("d_m and the mask's column overlap", dict(sets=[rset(mask=1, mask_col=3)], m=S(3))),
+        ("d_m is an unnamed base column", dict(m=S(3))),
+        ("d_report and named base overlap", dict(report=S(1, 56))),
+        ("d_report in an unnamed base column", dict(report=S(2))),
+        ("d_m and d_report overlap", dict(report=S(OUT[0].k, 56))),
+        ("d_m before d_report on one column", dict(m=S(0), report=S(0))),
+        ("the first column's d_report before the second's d_m", dict(m=S(1), report=S(0))),
+        ("base before d_m and d_report", dict(m=S(1), report=S(1, 8))),
+        ("bad MS_RANGE_FORM", dict(env={"MS_RANGE_FORM": "fast"})),
+        ("empty MS_RANGE_FORM", dict(env={"MS_RANGE_FORM": ""})),
+        ("MS_RANGE_FORM plain", dict(env={"MS_RANGE_FORM": "plain"})),
+        ("MS_RANGE_FORM lds", dict(env={"MS_RANGE_FORM": "lds"})),
+        ("overlap before MS_RANGE_FORM", dict(env={"MS_RANGE_FORM": "fast"}, m=S(0))),
+        ("n 0", dict(n=0)),
+        ("n 0 reads MS_RANGE_FORM", dict(n=0, env={"MS_RANGE_FORM": "fast"})),
+        ("checked: named column", dict(checked=True, base=[S(0), BAD_FP, S(2), S(3)])),
+        ("checked: the mask's column", dict(checked=True, base=WITH_BAD, sets=[rset(mask=1, mask_col=2)])),
+        ("checked: unnamed column", dict(checked=True, base=WITH_BAD)),
+        ("checked: d_m is an unnamed column", dict(checked=True, base=WITH_BAD, m=BAD_FP)),
+        ("checked: fp252", dict(checked=True, field=F252, base=[BAD_252, S(1), S(2), S(3)])),
+        ("checked: before MS_RANGE_FORM", dict(checked=True, base=[BAD_FP, S(1), S(2), S(3)], env={"MS_RANGE_FORM": "fast"})),
+        ("checked: n 0", dict(checked=True, n=0, base=[BAD_FP, S(1), S(2), S(3)])),
+    ]),
+    "ms_bitwise_columns": (call_bcols, [
+        ("accepted", {}),
+        ("accepted with one operand twice", dict(specs=[bspec(XOR, 1, 1)])),
+        ("accepted over fp252", dict(field=F252, specs=[bspec(OR, width=251)])),
+        ("null ctx", dict(ctx=False)),
+        ("null d_base", dict(base=None, nbase=4)),
+        ("null h_specs", dict(specs=None, nspecs=1)),
+        ("no specs", dict(specs=None)),
+        ("null d_report", dict(report=None)),
+        ("fq3", dict(field=FQ3)),
+        ("unknown field", dict(field=7)),
+        ("65 specs", dict(specs=[bspec()] * 65)),
+        ("rows 2^32 + 1", dict(n=BIG32)),
+        ("rows 2^32 are not refused for their number", dict(n=1 << 32, specs=[bspec(op=9)])),
+        ("null base column", dict(base=BASE_NULL2)),
+        ("op 3", dict(specs=[bspec(op=3)])),
+        ("op -1", dict(specs=[bspec(), bspec(op=-1, dst=3)])),
+        ("operand a 4", dict(specs=[bspec(a=4)])),
+        ("operand a -1", dict(specs=[bspec(a=-1)])),
+        ("operand b 4", dict(specs=[bspec(b=4)])),
+        ("operand b -1", dict(specs=[bspec(b=-1)])),
+        ("mask kind 3", dict(specs=[bspec(mask=3)])),
+        ("mask kind -1", dict(specs=[bspec(mask=-1)])),
+        ("mask column 4", dict(specs=[bspec(mask=1, mask_col=4)])),
+        ("mask column -1", dict(specs=[bspec(mask=2, mask_col=-1)])),
+        ("width 0", dict(specs=[bspec(width=0)])),
+        ("width 63 over fp", dict(specs=[bspec(width=63)])),
+        ("width 64 over fp", dict(specs=[bspec(width=64)])),
+        ("width 252 over fp252", dict(field=F252, specs=[bspec(width=252)])),
+        ("destination -1", dict(specs=[bspec(dst=-1)])),
+        ("destination 4", dict(specs=[bspec(dst=4)])),
+        ("op before a before b before mask before width before destination", dict(specs=[bspec(op=9, a=9, b=9, mask=9, width=0, dst=9)])),
+        ("a before b before mask before width before destination", dict(specs=[bspec(a=9, b=9, mask=9, width=0, dst=9)])),
+        ("b before mask before width before destination", dict(specs=[bspec(b=9, mask=9, width=0, dst=9)])),
+        ("mask before width before destination", dict(specs=[bspec(mask=9, width=0, dst=9)])),
+        ("width before destination", dict(specs=[bspec(width=0, dst=9)])),
+        ("rows before specs", dict(n=BIG32, specs=[bspec(op=9)])),
+        ("count before null base column", dict(base=BASE_NULL2, specs=[bspec()] * 65)),
+        ("two specs with one destination", dict(specs=[bspec(), bspec(OR)])),
+        ("the first and third spec with one destination", dict(specs=[bspec(dst=3), bspec(dst=2), bspec(XOR, dst=3)])),
+        ("two specs' destinations in the same memory", dict(base=[S(0), S(1), S(2), S(2, 56)], specs=[bspec(dst=2), bspec(dst=3)])),
+        ("destination is operand a", dict(specs=[bspec(a=2)])),
+        ("destination is operand b", dict(specs=[bspec(b=2)])),
+        ("destination is another spec's operand", dict(specs=[bspec(dst=2), bspec(a=2, dst=3)])),
+        ("destination is a later spec's mask", dict(specs=[bspec(dst=2), bspec(dst=3, mask=1, mask_col=2)])),
+        ("destination and operand memory overlap", dict(base=[S(0), S(1), S(1, 56), S(3)])),
+        ("destination and mask memory overlap", dict(base=[S(0), S(1), S(2), S(2, 8)], specs=[bspec(mask=2, mask_col=3)])),
+        ("destination and unnamed column memory overlap goes through", dict(base=[S(0), S(1), S(2), S(2)])),
+        ("d_report and operand overlap", dict(report=S(1, 56))),
+        ("d_report and the mask's column overlap", dict(specs=[bspec(mask=2, mask_col=3)], report=S(3))),
+        ("d_report and destination overlap", dict(report=S(2, 8))),
+        ("d_report in an unnamed column", dict(report=S(3))),
+        ("the first spec's operand before the second's destination", dict(specs=[bspec(a=2), bspec(dst=2)])),
+        ("two specs' destinations before the second's operand", dict(specs=[bspec(dst=2), bspec(a=2, dst=2)])),
+        ("a destination before a read column for d_report", dict(base=[S(0), S(1), S(2), S(2, 64)], specs=[bspec(a=3)], report=S(2, 56))),
+        ("d_report and the first's destination before a later spec's destination", dict(specs=[bspec(), bspec(OR)], report=S(2))),
+        ("the first spec's operand before d_report and its destination", dict(specs=[bspec(a=2)], report=S(2))),
+        ("n 0", dict(n=0)),
+        ("n 0 passes the memory overlaps", dict(n=0, base=[S(0), S(1), S(0), S(3)], report=S(0))),
+        ("n 0 still refuses a destination that is an operand", dict(n=0, specs=[bspec(b=2)])),
+        ("checked: operand a", dict(checked=True, base=[BAD_FP, S(1), S(2), S(3)])),
+        ("checked: operand b", dict(checked=True, base=[S(0), BAD_FP, S(2), S(3)])),
+        ("checked: the mask's column", dict(checked=True, base=[S(0), S(1), S(2), BAD_FP], specs=[bspec(mask=1, mask_col=3)])),
+        ("checked: unnamed column", dict(checked=True, base=[S(0), S(1), S(2), BAD_FP])),
+        ("checked: destination", dict(checked=True, base=WITH_BAD)),
+        ("checked: fp252", dict(checked=True, field=F252, base=[S(0), BAD_252, S(2), S(3)])),
+        ("checked: overlap first", dict(checked=True, base=[BAD_FP, S(1), S(2), S(3)], report=S(2))),
+        ("checked: n 0", dict(checked=True, n=0, base=[BAD_FP, S(1), S(2), S(3)])),
+        ("checked: no specs", dict(checked=True, specs=None, base=[BAD_FP, S(1), S(2), S(3)])),
+    ]),
+    "ms_bitwise_table": (call_btable, [
+        ("accepted", {}),
+        ("accepted without an op column", dict(top=None)),
+        ("accepted over fp252", dict(field=F252)),
+        ("accepted with one op", dict(ops=[XOR], n_t=4)),
+        ("null ctx", dict(ctx=False)),
+        ("null h_ops", dict(ops=None, nops=3)),
+        ("null d_tx", dict(tx=None)),
+        ("null d_ty", dict(ty=None)),
+        ("null d_tz", dict(tz=None)),
+        ("fq3", dict(field=FQ3)),
+        ("unknown field", dict(field=7)),
+        ("0 bits", dict(bits=0)),
+        ("13 bits", dict(bits=13)),
+        ("0 ops", dict(ops=[AND], nops=0)),
+        ("4 ops", dict(ops=[AND, OR, XOR, AND])),
+        ("op 3", dict(ops=[AND, 3])),
+        ("op -1", dict(ops=[-1])),
+        ("op named twice", dict(ops=[OR, XOR, OR])),
+        ("unknown op before an op named twice", dict(ops=[5, OR, OR])),
+        ("an op named twice before an unknown one", dict(ops=[OR, OR, 5])),
+        ("2 ops over 12 bits", dict(bits=12, ops=[AND, OR], n_t=1 << 25)),
+        ("1 op over 12 bits is 2^24 rows, too few elements", dict(bits=12, ops=[AND], n_t=(1 << 24) - 1)),
+        ("11 elements", dict(n_t=11)),
+        ("bits before ops before elements", dict(bits=0, ops=[9], n_t=0)),
+        ("ops before elements", dict(ops=[9], n_t=0)),
+        ("d_tx and d_ty overlap", dict(ty=S(TX.k, 88))),
+        ("d_tx and d_tz overlap", dict(tz=S(TX.k, 88))),
+        ("d_ty and d_tz overlap", dict(tz=S(TY.k, 88))),
+        ("d_tx and d_top overlap", dict(top=S(TX.k, 88))),
+        ("d_ty and d_top overlap", dict(top=S(TY.k, 88))),
+        ("d_tz and d_top overlap", dict(top=S(TZ.k, 88))),
+        ("columns that touch do not overlap", dict(ty=S(TX.k, 96))),
+        ("d_tx and d_ty before d_tx and d_tz", dict(ty=TX, tz=TX)),
+        ("d_ty and d_tz before d_tx and d_top", dict(tz=TY, top=TX)),
+        ("elements before overlap", dict(n_t=11, ty=TX)),
+    ]),
+    "ms_bitwise_multiplicities": (call_bmult, [
+        ("accepted", {}),
+        ("accepted over fp252", dict(field=F252)),
+        ("null ctx", dict(ctx=False)),
+        ("null d_base", dict(base=None, nbase=4)),
+        ("null h_ops", dict(ops=None, nops=2)),
+        ("null h_sets", dict(sets=None, nsets=1)),
+        ("no sets", dict(sets=None)),
+        ("null d_m", dict(m=None)),
+        ("null d_report", dict(report=None)),
+        ("fq3", dict(field=FQ3)),
+        ("unknown field", dict(field=7)),
+        ("0 bits", dict(bits=0)),
+        ("13 bits", dict(bits=13)),
+        ("0 ops", dict(ops=[AND], nops=0)),
+        ("4 ops", dict(ops=[AND, OR, XOR, AND])),
+        ("table op 3", dict(ops=[AND, 3])),
+        ("table op named twice", dict(ops=[XOR, XOR])),
+        ("2 ops over 12 bits", dict(bits=12, ops=[AND, OR], n_m=1 << 25)),
+        ("65 sets", dict(sets=[bset()] * 65)),
+        ("d_m of 7", dict(n_m=7)),
+        ("null base column", dict(base=BASE_NULL2)),
+        ("set op 5", dict(sets=[bset(op=5)])),
+        ("set op not in the table", dict(sets=[bset(), bset(OR)])),
+        ("operand a 4", dict(sets=[bset(a=4)])),
+        ("operand a -1", dict(sets=[bset(a=-1)])),
+        ("operand b 4", dict(sets=[bset(b=4)])),
+        ("operand b -1", dict(sets=[bset(b=-1)])),
+        ("result -2", dict(sets=[bset(c=-2)])),
+        ("result 4", dict(sets=[bset(c=4)])),
+        ("mask kind 3", dict(sets=[bset(mask=3)])),
+        ("mask kind -1", dict(sets=[bset(mask=-1)])),
+        ("mask column 4", dict(sets=[bset(mask=1, mask_col=4)])),
+        ("mask column -1", dict(sets=[bset(mask=2, mask_col=-1)])),
+        ("0 limbs", dict(sets=[bset(nlimbs=0)])),
+        ("257 limbs", dict(sets=[bset(nlimbs=257)])),
+        ("63 limbs of 1 bit over fp", dict(sets=[bset(nlimbs=63)])),
+        ("64 limbs of 1 bit over fp", dict(sets=[bset(nlimbs=64)])),
+        ("252 limbs of 1 bit over fp252", dict(field=F252, sets=[bset(nlimbs=252)])),
+        ("6 limbs of 12 bits over fp", dict(bits=12, ops=[AND], n_m=1 << 24, sets=[bset(nlimbs=6)])),
+        ("bits before ops before sets before d_m before null base column", dict(base=BASE_NULL2, bits=0, ops=[9], sets=[bset()] * 65, n_m=0)),
+        ("ops before sets before d_m before null base column", dict(base=BASE_NULL2, ops=[9], sets=[bset()] * 65, n_m=0)),
+        ("sets before d_m before null base column", dict(base=BASE_NULL2, sets=[bset()] * 65, n_m=0)),
+        ("d_m before null base column", dict(base=BASE_NULL2, n_m=0)),
+        ("unknown op before an op not in the table before a before b before result before mask before limbs",
+         dict(sets=[bset(op=5, a=9, b=9, c=9, mask=9, nlimbs=0)])),
+        ("an op not in the table before a before b before result before mask before limbs", dict(sets=[bset(op=OR, a=9, b=9, c=9, mask=9, nlimbs=0)])),
+        ("a before b before result before mask before limbs", dict(sets=[bset(a=9, b=9, c=9, mask=9, nlimbs=0)])),
+        ("b before result before mask before limbs", dict(sets=[bset(b=9, c=-9, mask=9, nlimbs=0)])),
+        ("result before mask before limbs", dict(sets=[bset(c=-9, mask=9, nlimbs=0)])),
+        ("mask before limbs", dict(sets=[bset(mask=9, nlimbs=0)])),
+        ("limbs before their width", dict(sets=[bset(nlimbs=300)])),
+        ("rows 2^32 + 1", dict(n=BIG32)),
+        ("2 limbs a row over 2^31 rows", dict(n=1 << 31, sets=[bset()])),
+        ("1 limb a row over 2^32 rows", dict(n=1 << 32, sets=[bset(nlimbs=1)])),
+        ("set before rows", dict(n=BIG32, sets=[bset(a=4)])),
+        ("rows before counters", dict(n=BIG32, sets=[bset()] * 64)),
+        ("d_m and operand a overlap", dict(m=S(0, 56))),
+        ("d_m and operand b overlap", dict(m=S(1, 8))),
+        ("d_m and the result column overlap", dict(m=S(2))),
+        ("d_m and the mask's column overlap", dict(sets=[bset(mask=1, mask_col=3)], m=S(3))),
+        ("d_m is an unnamed base column", dict(m=S(3))),
+        ("d_report and named base overlap", dict(report=S(2, 56))),
+        ("d_report in an unnamed base column", dict(report=S(3))),
+        ("d_m and d_report overlap", dict(report=S(OUT[0].k, 56))),
+        ("d_m before d_report on one column", dict(m=S(0), report=S(0))),
+        ("the first column's d_report before the second's d_m", dict(m=S(1), report=S(0))),
+        ("base before d_m and d_report", dict(m=S(1), report=S(1, 8))),
+        ("bad MS_BITWISE_FORM", dict(env={"MS_BITWISE_FORM": "fast"})),
+        ("empty MS_BITWISE_FORM", dict(env={"MS_BITWISE_FORM": ""})),
+        ("MS_BITWISE_FORM plain", dict(env={"MS_BITWISE_FORM": "plain"})),
+        ("MS_BITWISE_FORM lds", dict(env={"MS_BITWISE_FORM": "lds"})),
+        ("overlap before MS_BITWISE_FORM", dict(env={"MS_BITWISE_FORM": "fast"}, m=S(0))),
+        ("n 0", dict(n=0)),
+        ("n 0 reads MS_BITWISE_FORM", dict(n=0, env={"MS_BITWISE_FORM": "fast"})),
+        ("checked: operand a", dict(checked=True, base=[BAD_FP, S(1), S(2), S(3)])),
+        ("checked: operand b", dict(checked=True, base=[S(0), BAD_FP, S(2), S(3)])),
+        ("checked: the result column", dict(checked=True, base=WITH_BAD)),
+        ("checked: the mask's column", dict(checked=True, base=[S(0), S(1), S(2), BAD_FP], sets=[bset(mask=1, mask_col=3)])),
+        ("checked: unnamed column", dict(checked=True, base=[S(0), S(1), S(2), BAD_FP])),
+        ("checked: d_m is an unnamed column", dict(checked=True, base=[S(0), S(1), S(2), BAD_FP], m=BAD_FP)),
+        ("checked: fp252", dict(checked=True, field=F252, base=[BAD_252, S(1), S(2), S(3)])),
+        ("checked: before MS_BITWISE_FORM", dict(checked=True, base=[BAD_FP, S(1), S(2), S(3)], env={"MS_BITWISE_FORM": "fast"})),
+        ("checked: n 0", dict(checked=True, n=0, base=[BAD_FP, S(1), S(2), S(3)])),
+    ]),
 }
 
 
@@ -452,12 +825,16 @@ def replay(kind, entry):
     out = []
     for case, args in cases:
         env = Env(kind)
+        args = dict(args)
+        setenv = args.pop("env", {})
         try:
-            args = dict(args)
             env.L.check(env.L.ms_ctx_set_checked(env.h, 1 if args.pop("checked", False) else 0))
+            os.environ.update(setenv)
             rc = fn(env, **args)
             out.append([entry, case, rc, env.L.ms_last_error().decode() if rc else None])
         finally:
+            for name in setenv:
+                del os.environ[name]
             env.close()
     return out
 
